@@ -7,7 +7,15 @@ re-encryption + Bayer-Groth prover) and `verify_shuffle`, with every input alrea
 Synthetic data: random ciphertext decks [REF src/discrete_log_cards/tests.rs:187] obtained by re-encrypting one
 random base deck on the GPU; masking factors uniform below 2^251; uniform permutations; random prover seeds.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, checks the status words of what it timed and prints the JSON line.  `--full`
+adds everything else the line can carry: the comparison of one timed proof with the oracle (`config.parity_vs_oracle`), the
+roofline of the timed region (per-kernel HIP events: `roofline`), clock / power telemetry, the extra measurements beside the
+headline (pairs workload, N = 1: per-equation, rejection, keyed, batch curve, host-buffer API, default table) and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed step computed -- shuffled decks, proofs and status words, a fixed sample of rows
+when the batch is larger than 64 MB allows -- as DIR/<name>.npy (bytes as float32, status words as float64): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one rank per GPU.  Started from a plain shell, bench.py launches the N ranks ITSELF (it re-executes under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); started by the driver under
@@ -22,8 +30,8 @@ Workloads (`--workload`, BASELINE.json's configs):
            own aggregate key (keyed batches); every link proved (T proofs per launch) and verified [REF examples/round.rs:268-350]
   mixed    (config 5) a stream of independent jobs, 50 % prove jobs / 50 % verify jobs (the proofs of the previous step)
 
-`roofline` is measured live with HIP events on the engine's own stream around every kernel launch of the timed region;
-`cpu_baseline` times the oracle's single-threaded C++ restatement (arkworks-style algorithms) on a bounded sample of
+`roofline` (--full) is measured live with HIP events on the engine's own stream around every kernel launch of the timed region;
+`cpu_baseline` (--full) times the oracle's single-threaded C++ restatement (arkworks-style algorithms) on a bounded sample of
 the same workload on this box's host cores.
 """
 import argparse
@@ -228,6 +236,40 @@ def shard_range(total, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+DUMP_BYTES_MAX = 60 * 10**6    # --dump-outputs: the rows written per rank stay below 64 MB with the .npy headers
+DUMP_SEED = 20240917
+
+
+def dump_rows(total, row_bytes, budget=DUMP_BYTES_MAX):
+    """rows of a `total`-row output that --dump-outputs writes: all of them if they fit the budget, else a fixed seeded sample
+    (sorted), the same for every run with the same batch"""
+    import numpy as np
+    keep = max(1, min(total, budget // max(1, row_bytes)))
+    if keep == total:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=keep, replace=False))
+
+
+def write_outputs(out_dir, arrays, prefix=""):
+    """--dump-outputs: `arrays` = {name: tensor whose first axis is the proof (row)}, every one of the same length; writes the rows
+    dump_rows() picks as out_dir/<prefix><name>.npy -- bytes as float32, wider integers (status words) as float64 -- and the row
+    numbers as out_dir/<prefix>rows.npy"""
+    import numpy as np
+    import torch
+    total = {int(t.shape[0]) for t in arrays.values()}
+    assert len(total) == 1, "outputs of different lengths: %s" % total
+    total = total.pop()
+    out_dt = {name: np.float32 if t.dtype == torch.uint8 else np.float64 for name, t in arrays.items()}
+    row_bytes = sum(t[0].numel() * np.dtype(out_dt[name]).itemsize for name, t in arrays.items()) + 8
+    rows = dump_rows(total, row_bytes)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        sel = t if len(rows) == total else t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), sel.cpu().numpy().astype(out_dt[name]))
+    np.save(os.path.join(out_dir, prefix + "rows.npy"), rows.astype(np.float64))
+    return rows
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -372,7 +414,14 @@ def main():
                     help="test hook: sha256 of every rank's outputs of the last step in config.digests (inputs are seeded per "
                          "block of --seed-block proofs, so a sharded run and an unsharded run of the same blocks must agree)")
     ap.add_argument("--seed-block", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed sample of rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: oracle parity, roofline, telemetry, the extra "
+                         "measurements in config and cpu_baseline (a plain run times the steps and prints the line)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -547,12 +596,13 @@ def main():
             t.reserve(Bs)
         keys = make_keys(args.keyed, B) if args.keyed > 0 else None
         for e in engines:
-            e.profile_enable(True)
+            e.profile_enable(args.full)
         decks = prime_decks(B)
         priming_launches = {}       # per-kernel launches of the untimed priming prove (tools/pmc_summary.py skips them)
         for e in engines:
-            for k, (cnt, _) in e.profile_report().items():
-                priming_launches[k] = priming_launches.get(k, 0) + cnt
+            if args.full:
+                for k, (cnt, _) in e.profile_report().items():
+                    priming_launches[k] = priming_launches.get(k, 0) + cnt
             e.profile_enable(False)
         # (--pipeline D: a verify call's inputs stay untouched until D further verify calls have returned -> D + 1 sets of prover outputs)
         out_sets = [(torch.empty(B, N * CB, dtype=torch.uint8, device=gpu), torch.empty(B, proof_bytes, dtype=torch.uint8, device=gpu),
@@ -618,6 +668,14 @@ def main():
                 hh.update(out_proofs[s_].cpu().numpy().tobytes())
                 h.append(hh.hexdigest())
             return h
+
+        def last_outputs():
+            # (--pipeline D: the last step wrote the set before the one the rotation points at next)
+            od, op_, sv = out_sets[(rot["i"] - 1) % len(out_sets)]
+            outs = {"shuffled_decks": od, "proofs": op_, "prove_status": st_p, "verify_status": sv}
+            if args.validated_once:
+                outs.update(validate_status_decks=st_val, validate_status_shuffled=st_val2)
+            return outs
     # =============================================================================================== workload: chain32
     elif workload == "chain32":
         # T tables per GPU, `players` dependent shuffles each; table t has its own aggregate key (keyed batches); link j of
@@ -697,6 +755,11 @@ def main():
             hh = hashlib.sha256()
             hh.update(chain[L].cpu().numpy().tobytes())
             return [hh.hexdigest()]
+
+        def last_outputs():
+            # every link of every table, link j of table t in row j T + t (the layout of the chain calls)
+            return {"shuffled_decks": chain[1:].view(L * T, -1), "proofs": proofs.view(L * T, -1), "prove_status": st_p.view(-1),
+                    "verify_status": st_v.view(-1)}
         table = keyless
         tables = [keyless]
     # =============================================================================================== workload: mixed
@@ -738,27 +801,35 @@ def main():
             hh.update(out_proofs[1 - state["cur"]].cpu().numpy().tobytes())
             return [hh.hexdigest()]
 
+        def last_outputs():
+            # the last step's prove jobs, and the verdicts of its verify jobs (on the proofs of the step before)
+            c = 1 - state["cur"]
+            return {"shuffled_decks": out_decks[c], "proofs": out_proofs[c], "prove_status": st_p, "verify_status": st_v}
+
     # ---- timed region: W warm-up steps, barrier + synchronize, K steps, barrier + synchronize
     for _ in range(args.warmup):
         step()
     barrier()
-    for e in engines:
-        e.profile_enable(True)
-    tele = Telemetry(local)
-    tele.start()
+    # (--full: per-kernel HIP events and the clock / power sampling thread run inside the timed region, as they always did there)
+    if args.full:
+        for e in engines:
+            e.profile_enable(True)
+        tele = Telemetry(local)
+        tele.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     my_enqueue = time.perf_counter() - t0      # every call of the K steps has returned (a verify call returns with its screening verdict)
     barrier()
     my_elapsed = time.perf_counter() - t0
-    my_sclk, my_power, my_samples = tele.stop()
+    my_sclk, my_power, my_samples = tele.stop() if args.full else (-1.0, -1.0, 0.0)
     prof = {}
-    for e in engines:
-        for k, (cnt, ms) in e.profile_report().items():
-            c0, m0 = prof.get(k, (0, 0.0))
-            prof[k] = (c0 + cnt, m0 + ms)
-        e.profile_enable(False)
+    if args.full:
+        for e in engines:
+            for k, (cnt, ms) in e.profile_report().items():
+                c0, m0 = prof.get(k, (0, 0.0))
+                prof[k] = (c0 + cnt, m0 + ms)
+            e.profile_enable(False)
     elapsed = reduce_max(my_elapsed, dev)
     hbm_used_gb = round((torch.cuda.mem_get_info(local)[1] - torch.cuda.mem_get_info(local)[0]) / 1e9, 1)
 
@@ -768,10 +839,12 @@ def main():
     total_proofs = sum(r[0] for r in rows)
     total_bad = int(sum(r[1] for r in rows))
     assert total_bad == 0, "%d proofs failed (per rank: %s)" % (total_bad, [int(r[1]) for r in rows])
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, last_outputs(), "" if world == 1 else "rank%d_" % rank)
     if args.digest:
         digests = gather_objects(digest())
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import coracle as co
         co.build()
         pk_b, d_in, f_in, p_in, s_in, d_out, pr_out = parity_inputs()
@@ -782,7 +855,7 @@ def main():
     value = total_proofs / elapsed
 
     # ---- the conditions of the headline, measured beside it (pairs workload, N = 1): one step each, same batch
-    if workload == "pairs" and world == 1 and not args.no_extras and args.keyed == 0 and not args.per_equation and S == 1:
+    if args.full and workload == "pairs" and world == 1 and not args.no_extras and args.keyed == 0 and not args.per_equation and S == 1:
         def timed_step(fn):
             fn()
             barrier()
@@ -965,249 +1038,251 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the dominant kernel (live HIP-event timings of the timed region)
-    stats = table.plan_stats()
     # group verification (include/mpshuffle.h: mp_set_group_verify): the verifier's screen of this batch is one bucket-method MSM per group of
     # `gl` proofs -- every point of the group's proofs once, the n + 5 fixed bases once per group -- instead of one Straus MSM per proof
     gl = 0
     if workload in ("pairs", "mixed") and not args.per_equation and args.keyed == 0:
         gl = table.group_size(Bs if workload == "pairs" else B // 2)
-    # chain verification (mp_set_chain_group / mp_set_chain_slice): the chains of chain_G tables share one equation, a call's tables go in
-    # passes of chain_pass tables (what the free memory holds of the 68 KB of workspace per link in flight)
-    chain_G, chain_pass = 1, None
-    if workload == "chain32" and not args.per_link_verify:
-        chain_pass = table.chain_last_slice() or B
-        chain_G = max(1, table.chain_group_size(chain_pass, extras["chain_links_per_equation"], True))
-        extras["chain_tables_per_equation"], extras["chain_tables_per_pass"] = chain_G, chain_pass
-    SCALAR_BITS = {"stark": 252, "bn254": 254, "secp256k1": 256, "bls12_377": 253}[curve]
+    roofline, rows_k = None, []
+    if args.full:
+        # ---- roofline of the dominant kernel (live HIP-event timings of the timed region)
+        stats = table.plan_stats()
+        # chain verification (mp_set_chain_group / mp_set_chain_slice): the chains of chain_G tables share one equation, a call's tables go in
+        # passes of chain_pass tables (what the free memory holds of the 68 KB of workspace per link in flight)
+        chain_G, chain_pass = 1, None
+        if workload == "chain32" and not args.per_link_verify:
+            chain_pass = table.chain_last_slice() or B
+            chain_G = max(1, table.chain_group_size(chain_pass, extras["chain_links_per_equation"], True))
+            extras["chain_tables_per_equation"], extras["chain_tables_per_pass"] = chain_G, chain_pass
+        SCALAR_BITS = {"stark": 252, "bn254": 254, "secp256k1": 256, "bls12_377": 253}[curve]
 
-    def bucket_geometry(K):
-        """window width the engine picks for a bucket-method MSM of K terms (kernels_bucket.hpp bk_bits_for), its windows per scalar,
-        buckets per lane and the point additions of the wave-wide reduction of one window"""
-        c = 14 if K >= 200000 else (12 if K >= 50000 else (11 if K >= 40000 else (10 if K >= 12000 else (9 if K >= 6000 else 8))))      # (12 and 13: the split pipeline, one reducing wave per window)
-        nb = (1 << (c - 1)) // 64
-        return {"bits": c, "windows": (SCALAR_BITS + c - 1) // c, "buckets_per_lane": nb, "reduction_adds": 13 + 2 * nb - 3}      # (round 6: min(k, q - k) is recoded: ceil(bits / c) windows)
-    per_proof_pts = 4 * N + 11 * m + 8
-    geo_own = bucket_geometry(per_proof_pts + 1)          # a proof's own bucket jobs (large decks: the merged equation and the prover's long products)
-    geo_grp = None
-    if gl:
-        geo_grp = bucket_geometry(gl * per_proof_pts)
-        # (large decks: the per-proof screen ran the merged equation as a bucket job of its own; the group equation replaces it)
-        own_terms = stats.get("bucket_terms", 0) - (per_proof_pts + 1 if stats["verify"].get("var_terms", 0) == 0 and stats.get("bucket_terms", 0) >= per_proof_pts else 0)
-        own_jobs = stats.get("bucket_jobs", 0) - (1 if own_terms != stats.get("bucket_terms", 0) else 0)
-        stats["verify"] = {"fixed_terms": (n + 5) / gl, "var_terms": 0, "fixed_jobs": 4.0 / gl, "var_jobs": 0, "table_bases": 0, "combine_terms": 5.0 / gl}
-        stats["bucket_terms"], stats["bucket_jobs"] = max(own_terms, 0), max(own_jobs, 0)
-        stats["group_terms"] = per_proof_pts
-        stats["group_jobs"] = 1.0 / gl
-        stats["verify_group_size"] = gl
-        stats["group_bucket_geometry"] = geo_grp
-    dom = max(prof.items(), key=lambda kv: kv[1][1])
-    dom_name, (dom_count, dom_ms) = dom
-    kernel_ms_total = sum(v[1] for v in prof.values())
+        def bucket_geometry(K):
+            """window width the engine picks for a bucket-method MSM of K terms (kernels_bucket.hpp bk_bits_for), its windows per scalar,
+            buckets per lane and the point additions of the wave-wide reduction of one window"""
+            c = 14 if K >= 200000 else (12 if K >= 50000 else (11 if K >= 40000 else (10 if K >= 12000 else (9 if K >= 6000 else 8))))      # (12 and 13: the split pipeline, one reducing wave per window)
+            nb = (1 << (c - 1)) // 64
+            return {"bits": c, "windows": (SCALAR_BITS + c - 1) // c, "buckets_per_lane": nb, "reduction_adds": 13 + 2 * nb - 3}      # (round 6: min(k, q - k) is recoded: ceil(bits / c) windows)
+        per_proof_pts = 4 * N + 11 * m + 8
+        geo_own = bucket_geometry(per_proof_pts + 1)          # a proof's own bucket jobs (large decks: the merged equation and the prover's long products)
+        geo_grp = None
+        if gl:
+            geo_grp = bucket_geometry(gl * per_proof_pts)
+            # (large decks: the per-proof screen ran the merged equation as a bucket job of its own; the group equation replaces it)
+            own_terms = stats.get("bucket_terms", 0) - (per_proof_pts + 1 if stats["verify"].get("var_terms", 0) == 0 and stats.get("bucket_terms", 0) >= per_proof_pts else 0)
+            own_jobs = stats.get("bucket_jobs", 0) - (1 if own_terms != stats.get("bucket_terms", 0) else 0)
+            stats["verify"] = {"fixed_terms": (n + 5) / gl, "var_terms": 0, "fixed_jobs": 4.0 / gl, "var_jobs": 0, "table_bases": 0, "combine_terms": 5.0 / gl}
+            stats["bucket_terms"], stats["bucket_jobs"] = max(own_terms, 0), max(own_jobs, 0)
+            stats["group_terms"] = per_proof_pts
+            stats["group_jobs"] = 1.0 / gl
+            stats["verify_group_size"] = gl
+            stats["group_bucket_geometry"] = geo_grp
+        dom = max(prof.items(), key=lambda kv: kv[1][1])
+        dom_name, (dom_count, dom_ms) = dom
+        kernel_ms_total = sum(v[1] for v in prof.values())
 
-    def alg_bytes_per_proof(kernel):
-        """ALGORITHMIC bytes one proof needs from this kernel class in one step (prove + verify launches):
-        scalars 32 B, points PB, Jacobian results 1.5 PB ("algorithmic bytes")."""
-        pv = [stats["prove"], stats["verify"]]
-        if kernel == "k_var_msm":
-            return sum(s["var_terms"] * (32 + PB) + s["var_jobs"] * 3 * PB // 2 for s in pv)
-        if kernel in ("k_bucket_msm", "k_bucket_acc"):
-            return (stats.get("bucket_terms", 0) + stats.get("group_terms", 0)) * (32 + PB) + (stats.get("bucket_jobs", 0) + stats.get("group_jobs", 0)) * 3 * PB // 2
-        if kernel == "k_fixed_msm":
-            return sum(s["fixed_terms"] * 32 + s["fixed_jobs"] * 3 * PB // 2 for s in pv)
-        if kernel == "k_table":
-            return sum(s["table_bases"] * (PB + 16 * PB) for s in pv)
-        if kernel == "k_remask":          # the deck, one masking factor per card, the re-encrypted deck as Jacobian points
-            return 2 * N * PB + N * 32 + 2 * N * 3 * PB // 2
-        if kernel == "k_normalize":
-            return sum(s["table_bases"] * 16 * (3 * PB // 2 + PB) for s in pv)
-        return None
-    whole_path_bytes = (2 * N * PB + N * 32 + 4 * N + (n + 4) * PB) + (2 * N * PB + proof_bytes) + (4 * N * PB + proof_bytes + (n + 4) * PB)   # SURVEY 8d4
-    per_proof = alg_bytes_per_proof(dom_name) or whole_path_bytes
-    # per-launch figures: summed over the launches of the timed region
-    dom_bytes = per_proof * total_proofs / world
-    achieved_gbs = dom_bytes / (dom_ms * 1e-3) / 1e9
-    # multiply-add count of one prove+verify: static plan (stats) x instruction counts of the compiled group law
-    mc = load_mad_counts(curve)
-    int_mul = None
-    if mc:
-        vw, fw = stats["var_windows"], stats["fixed_windows"]
-        mads_per_proof = 0
-        chain_eq = workload == "chain32" and not args.per_link_verify
-        for side in ("prove", "verify"):
-            st_ = stats[side]
-            if side == "verify" and chain_eq:
-                # one chain equation per table instead of L per-link equations (engine_core.hpp build_chain_plan): a bucket MSM
-                # over the (L+1) decks, the L proofs' points and the key, plus one fixed-base term per shared generator
-                # (round 5: the chains of chain_G tables in one equation; a chain longer than --chain-max-links in consecutive sub-chains)
-                L_, lc_ = args.players, extras["chain_links_per_equation"]
-                nsub_ = (L_ + lc_ - 1) // lc_
-                k_terms = (lc_ + 1) * 2 * N + lc_ * (11 * m + 7) + 1
-                geo_c = bucket_geometry(chain_G * k_terms)
-                bwc = geo_c["windows"]
-                fmc = mc["field"]
-                red = geo_c["reduction_adds"] * 64 * (12 * fmc["mul"] + 2 * fmc["sqr"]) + geo_c["bits"] * mc["dbl"] + mc["jac"]
-                mads_per_proof += nsub_ * (k_terms * bwc * mc["madd"] + (bwc * red + (n + 2) * fw * mc["madd"]) / chain_G) / L_
+        def alg_bytes_per_proof(kernel):
+            """ALGORITHMIC bytes one proof needs from this kernel class in one step (prove + verify launches):
+            scalars 32 B, points PB, Jacobian results 1.5 PB ("algorithmic bytes")."""
+            pv = [stats["prove"], stats["verify"]]
+            if kernel == "k_var_msm":
+                return sum(s["var_terms"] * (32 + PB) + s["var_jobs"] * 3 * PB // 2 for s in pv)
+            if kernel in ("k_bucket_msm", "k_bucket_acc"):
+                return (stats.get("bucket_terms", 0) + stats.get("group_terms", 0)) * (32 + PB) + (stats.get("bucket_jobs", 0) + stats.get("group_jobs", 0)) * 3 * PB // 2
+            if kernel == "k_fixed_msm":
+                return sum(s["fixed_terms"] * 32 + s["fixed_jobs"] * 3 * PB // 2 for s in pv)
+            if kernel == "k_table":
+                return sum(s["table_bases"] * (PB + 16 * PB) for s in pv)
+            if kernel == "k_remask":          # the deck, one masking factor per card, the re-encrypted deck as Jacobian points
+                return 2 * N * PB + N * 32 + 2 * N * 3 * PB // 2
+            if kernel == "k_normalize":
+                return sum(s["table_bases"] * 16 * (3 * PB // 2 + PB) for s in pv)
+            return None
+        whole_path_bytes = (2 * N * PB + N * 32 + 4 * N + (n + 4) * PB) + (2 * N * PB + proof_bytes) + (4 * N * PB + proof_bytes + (n + 4) * PB)   # SURVEY 8d4
+        per_proof = alg_bytes_per_proof(dom_name) or whole_path_bytes
+        # per-launch figures: summed over the launches of the timed region
+        dom_bytes = per_proof * total_proofs / world
+        achieved_gbs = dom_bytes / (dom_ms * 1e-3) / 1e9
+        # multiply-add count of one prove+verify: static plan (stats) x instruction counts of the compiled group law
+        mc = load_mad_counts(curve)
+        int_mul = None
+        if mc:
+            vw, fw = stats["var_windows"], stats["fixed_windows"]
+            mads_per_proof = 0
+            chain_eq = workload == "chain32" and not args.per_link_verify
+            for side in ("prove", "verify"):
+                st_ = stats[side]
+                if side == "verify" and chain_eq:
+                    # one chain equation per table instead of L per-link equations (engine_core.hpp build_chain_plan): a bucket MSM
+                    # over the (L+1) decks, the L proofs' points and the key, plus one fixed-base term per shared generator
+                    # (round 5: the chains of chain_G tables in one equation; a chain longer than --chain-max-links in consecutive sub-chains)
+                    L_, lc_ = args.players, extras["chain_links_per_equation"]
+                    nsub_ = (L_ + lc_ - 1) // lc_
+                    k_terms = (lc_ + 1) * 2 * N + lc_ * (11 * m + 7) + 1
+                    geo_c = bucket_geometry(chain_G * k_terms)
+                    bwc = geo_c["windows"]
+                    fmc = mc["field"]
+                    red = geo_c["reduction_adds"] * 64 * (12 * fmc["mul"] + 2 * fmc["sqr"]) + geo_c["bits"] * mc["dbl"] + mc["jac"]
+                    mads_per_proof += nsub_ * (k_terms * bwc * mc["madd"] + (bwc * red + (n + 2) * fw * mc["madd"]) / chain_G) / L_
+                    continue
+                fixed_madds = st_["fixed_terms"] * fw
+                if side == "prove":
+                    fixed_madds -= N * (fw - 1)               # c_A commits pi(i)+1 <= N: one non-zero window per term
+                    fixed_madds += 2 * N * (fw + 1)           # re-encryption: 2N fixed-base scalar-muls + one addition each
+                    norm_points = 2 * N + 11 * m + 7          # shuffled deck + proof points
+                else:
+                    norm_points = 0
+                mads_per_proof += (fixed_madds + st_["var_terms"] * vw) * mc["madd"]
+                mads_per_proof += st_["var_jobs"] * (vw - 1) * 5 * mc["dbl"]
+                mads_per_proof += st_["table_bases"] * 15 * mc["aff"]
+                mads_per_proof += st_["combine_terms"] * mc["jac"] + norm_points * mc["norm"]
+            # Toom-Cook evaluation of the ciphertext polynomials (k_toom_points, kernels_msm.hpp): per vector position and pair +-x a
+            # Horner scheme in x^2 over the even and the odd coefficients (Jacobian: doubling 3M+(4+2a)S, mixed addition 8M+3S,
+            # addition 11M+5S), multiplications by the small integers x^2 and x as double-and-add
+            tm = stats.get("toom_points_m", 0)
+            if tm:
+                fmt = mc["field"]
+                jdbl = 3 * fmt["mul"] + (4 + 2 * a1_of(mc)) * fmt["sqr"]
+                jmadd = 8 * fmt["mul"] + 3 * fmt["sqr"]
+
+                def mul_small(k):
+                    return 0 if k == 1 else (k.bit_length() - 1) * jdbl + (bin(k).count("1") - 1) * mc["jac"]
+                top_even, top_odd = (tm - 1) & ~1, (tm - 1) if (tm - 1) & 1 else tm - 2
+                per_pos = 0
+                for p_ in range(tm - 1):
+                    x_ = 1 if p_ == 0 else (p_ + 1) // 2 + 1
+                    steps_ = top_even // 2 + (top_odd - 1) // 2
+                    per_pos += steps_ * (mul_small(x_ * x_) + jmadd) + mul_small(x_) + 2 * mc["jac"]
+                mads_per_proof += 2 * n * per_pos + (2 * tm - 2) * 2 * n * mc["norm"]        # + normalisation of the evaluated vectors
+            # bucket-method MSMs: one mixed addition per term and window; per (MSM, window) the wave-wide reduction on 64 lanes
+            # (XYZZ + XYZZ, 12M+2S; 13 + 2 NB - 3 of them) and the fold (c doublings + 1 addition)
+            bw = geo_own["windows"]
+            fm = mc["field"]
+            xyzz_add = 12 * fm["mul"] + 2 * fm["sqr"]
+            for terms_k, jobs_k, geo in (("bucket_terms", "bucket_jobs", geo_own), ("group_terms", "group_jobs", geo_grp)):
+                if geo:
+                    mads_per_proof += stats.get(terms_k, 0) * geo["windows"] * mc["madd"]
+                    mads_per_proof += stats.get(jobs_k, 0) * geo["windows"] * (geo["reduction_adds"] * 64 * xyzz_add + geo["bits"] * mc["dbl"] + mc["jac"])
+            mads = mads_per_proof * total_proofs / world
+            int_mul = {"bound": "v_mad_u64_u32 issue", "achieved": round(mads / (kernel_ms_total * 1e-3) / 1e9, 1),
+                       "peak": INT_MAD_PEAK_G, "unit": "Gmad/s",
+                       "frac": mads / (kernel_ms_total * 1e-3) / 1e9 / INT_MAD_PEAK_G,
+                       "mads_per_proof": int(mads_per_proof), "mads_per_op": {k: v for k, v in mc.items() if k not in ("field", "a1", "issue")},
+                       "plan_stats": stats, "bucket_windows": (geo_grp or geo_own)["windows"],
+                       "mads_per_field_op": mc["field"],
+                       "note": "32x32+64 multiply-adds (v_mad_u64_u32 + v_mad_i64_i32) counted in the gfx950 assembly of THIS build "
+                               "(mental-poker_amd/mad_counts.json, tools/gen_mad_counts.py) x static plan, over the kernel time of the WHOLE step; "
+                               "peak = 1024 SIMDs x 16 lanes/clk x 2.4 GHz (sustained in tools/microbench/roof.hip: 35.3 T/s at 2.28 GHz and 1.17 kW). "
+                               "The multiplies are ~55 % of the issue slots of the group law: the binding figure is roofline.compute"}
+        # ---- compute bound of the dominant kernel: VALU issue time.  Wave-level group operations of the kernel (static plan) x the issue
+        # cycles of one operation (4 x half-rate + 2 x full-rate VALU instructions of its main path, counted in the gfx950 ISA of this
+        # build) / 1024 SIMDs = the cycles every SIMD needs at the very least; divided by the kernel's measured time = the issue rate it
+        # sustained, against the shader clock (2.4 GHz maximum; the clock measured under this kernel if a PMC pass of this build exists)
+        compute = None
+        if mc and mc.get("issue"):
+            iss = mc["issue"]
+            vw, fw = stats["var_windows"], stats["fixed_windows"]
+            ops = None                      # per proof pair (prove + verify launches of one step), lane level
+            if dom_name == "k_var_msm":
+                # (chain32 with chain verification: the verifier's equation runs on the bucket kernel, only the prover uses k_var_msm)
+                sides = ("prove",) if (workload == "chain32" and not args.per_link_verify) else ("prove", "verify")
+                ops = {"madd": sum(stats[s_]["var_terms"] for s_ in sides) * vw,
+                       "dbl": sum(stats[s_]["var_jobs"] for s_ in sides) * (vw - 1) * 5}
+            elif dom_name == "k_fixed_msm":
+                ops = {"madd": sum(stats[s_]["fixed_terms"] for s_ in ("prove", "verify")) * fw - N * (fw - 1)}
+            elif dom_name == "k_remask":
+                ops = {"madd": 2 * N * (fw + 1)}
+            elif dom_name in ("k_bucket_msm", "k_bucket_acc") and "xadd" in iss:
+                if workload == "chain32" and not args.per_link_verify:
+                    L_, lc_ = args.players, extras["chain_links_per_equation"]
+                    nsub_ = (L_ + lc_ - 1) // lc_
+                    kc_ = (lc_ + 1) * 2 * N + lc_ * (11 * m + 7) + 1
+                    parts_ = [(nsub_ * kc_ / L_, nsub_ / (chain_G * L_), bucket_geometry(chain_G * kc_))]
+                else:
+                    parts_ = [(stats.get("bucket_terms", 0), stats.get("bucket_jobs", 0), geo_own)]
+                    if geo_grp:
+                        parts_.append((stats["group_terms"], stats["group_jobs"], geo_grp))
+                # one mixed addition per term and window (64 lanes share a window's terms evenly at best); per (MSM, window) the wave-wide
+                # reduction is 13 + 2 NB - 3 full additions on all 64 lanes
+                ops = {"madd": sum(t_ * g_["windows"] for t_, j_, g_ in parts_), "xadd": sum(j_ * g_["windows"] * g_["reduction_adds"] * 64 for t_, j_, g_ in parts_)}
+            if ops and sum(ops.values()) > 0:       # (plan_stats describes the throughput plan: small batches on the finer splits have no entry)
+                cyc_per_proof = sum(ops[k] * iss[k]["cycles"] for k in ops)                     # lane-level issue cycles x 1 lane
+                waves_cycles = cyc_per_proof * (total_proofs / world) / 64.0                        # wave-level instructions issue for 64 lanes at once
+                achieved_ghz = waves_cycles / SIMDS / (dom_ms * 1e-3) / 1e9
+                # second view, the one the SQ counters see: every VALU instruction takes one 4-cycle issue slot of its SIMD (in streams that
+                # mix the two classes the cheap instructions do not get their 2-cycle rate: roof microbenchmark, mad:cheap rows)
+                insts_per_proof = sum(ops[k] * (iss[k]["half_rate"] + iss[k]["full_rate"]) for k in ops)
+                slot_ginst = insts_per_proof * (total_proofs / world) / 64.0 / (dom_ms * 1e-3) / 1e9
+                slots = {"valu_insts_per_op": {k: iss[k]["half_rate"] + iss[k]["full_rate"] for k in ops},
+                         "achieved_G_wave_insts_per_s": round(slot_ginst, 2), "peak_G_wave_insts_per_s": SIMDS * CLK_MAX_GHZ / 4.0,
+                         "frac": slot_ginst / (SIMDS * CLK_MAX_GHZ / 4.0), "frac_at_measured_clock": None,
+                         "note": "one VALU instruction per 4-cycle slot per SIMD; static instruction counts x plan"}
+                compute = {"bound": "valu_issue", "kernel": dom_name, "achieved": round(achieved_ghz, 4), "peak": CLK_MAX_GHZ,
+                           "unit": "G issue-cycles/s per SIMD (= GHz of fully used VALU issue port)", "frac": achieved_ghz / CLK_MAX_GHZ,
+                           "ops_per_proof": {k: round(v, 1) for k, v in ops.items()},
+                           "issue_cycles_per_op": {k: iss[k] for k in ops},
+                           "clock_mhz": None, "peak_at_measured_clock": None, "frac_at_measured_clock": None, "issue_slots": slots,
+                           "note": "ideal issue time = sum over wave-level operations of (4 x half-rate + 2 x full-rate VALU instructions) / 1024 "
+                                   "SIMDs; instruction counts from the gfx950 ISA of this build (mad_counts.json: valu_issue), classes and "
+                                   "the no-co-issue rule from tools/microbench/roof.hip (profiles/r03_roof.json)"}
+        # HBM traffic of the dominant kernel: PMC pass (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs, gfx950 x2
+        # correction applied to FETCH_SIZE) of THIS build at THIS configuration, if one is committed under profiles/
+        src_hash = engine_source_hash()
+        traffic, traffic_src = None, None
+        pmc_path, pmc = find_pmc_summary(src_hash, curve, m, n, B, workload)
+        if pmc and dom_name in pmc.get("kernels", {}):
+            e_ = pmc["kernels"][dom_name]
+            traffic = e_.get("hbm_bytes_per_proof_per_step", e_["hbm_bytes_per_proof_per_step_corrected"]) * (total_proofs / world) / dom_count
+            traffic_src = pmc_path
+            if compute and e_.get("clock_mhz"):
+                # effective shader clock under this kernel = GRBM_GUI_ACTIVE / 8 XCDs / dispatch duration, both of the SAME profiled pass
+                compute["clock_mhz"] = round(e_["clock_mhz"], 1)
+                compute["peak_at_measured_clock"] = round(e_["clock_mhz"] / 1e3, 4)
+                compute["frac_at_measured_clock"] = min(1.0, compute["achieved"] / (e_["clock_mhz"] / 1e3))
+                compute["clock_source"] = pmc_path
+                compute["issue_slots"]["frac_at_measured_clock"] = min(1.0, compute["issue_slots"]["achieved_G_wave_insts_per_s"] / (SIMDS * e_["clock_mhz"] / 1e3 / 4.0))
+            if compute and e_.get("SQ_INSTS_VALU_per_launch"):
+                compute["valu_insts_per_launch_pmc"] = e_["SQ_INSTS_VALU_per_launch"]
+                # measured, not modelled: SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x shader cycles of the dispatch), same PMC pass
+                compute["issue_slots"]["measured_pmc"] = e_.get("valu_slot_utilisation")
+        roofline = {
+            "bound": "hbm", "kernel": dom_name, "achieved": round(achieved_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+            "avg_launch_ms": dom_ms / dom_count, "launches": dom_count,
+            "alg_bytes_per_launch": dom_bytes / dom_count, "alg_bytes_per_proof": per_proof,
+            "note": "path is bound by VALU issue, not by HBM (SURVEY 8d3): see compute (dominant kernel) and int_mul (whole step)",
+            "compute": compute,
+            "int_mul": int_mul,
+            "whole_path_hbm_frac": value / world * whole_path_bytes / 1e9 / HBM_PEAK_GBS,
+            "kernels_ms": {k: round(v[1], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+            "kernel_launches": {k: v[0] for k, v in prof.items()}, "priming_launches": priming_launches,
+            "engine_src": src_hash,
+        }
+
+        # one row per kernel that takes >= 3 % of the step: per-launch time, algorithmic bytes per launch and their fraction of the HBM peak,
+        # and -- from the PMC pass of THIS build at THIS configuration, if one is committed under profiles/ -- the VALU issue slots it used,
+        # its clock and the bytes the counters saw per launch
+        rows_k = []
+        for k_, (cnt_, ms_) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
+            if ms_ < 0.03 * kernel_ms_total or not cnt_:
                 continue
-            fixed_madds = st_["fixed_terms"] * fw
-            if side == "prove":
-                fixed_madds -= N * (fw - 1)               # c_A commits pi(i)+1 <= N: one non-zero window per term
-                fixed_madds += 2 * N * (fw + 1)           # re-encryption: 2N fixed-base scalar-muls + one addition each
-                norm_points = 2 * N + 11 * m + 7          # shuffled deck + proof points
-            else:
-                norm_points = 0
-            mads_per_proof += (fixed_madds + st_["var_terms"] * vw) * mc["madd"]
-            mads_per_proof += st_["var_jobs"] * (vw - 1) * 5 * mc["dbl"]
-            mads_per_proof += st_["table_bases"] * 15 * mc["aff"]
-            mads_per_proof += st_["combine_terms"] * mc["jac"] + norm_points * mc["norm"]
-        # Toom-Cook evaluation of the ciphertext polynomials (k_toom_points, kernels_msm.hpp): per vector position and pair +-x a
-        # Horner scheme in x^2 over the even and the odd coefficients (Jacobian: doubling 3M+(4+2a)S, mixed addition 8M+3S,
-        # addition 11M+5S), multiplications by the small integers x^2 and x as double-and-add
-        tm = stats.get("toom_points_m", 0)
-        if tm:
-            fmt = mc["field"]
-            jdbl = 3 * fmt["mul"] + (4 + 2 * a1_of(mc)) * fmt["sqr"]
-            jmadd = 8 * fmt["mul"] + 3 * fmt["sqr"]
-
-            def mul_small(k):
-                return 0 if k == 1 else (k.bit_length() - 1) * jdbl + (bin(k).count("1") - 1) * mc["jac"]
-            top_even, top_odd = (tm - 1) & ~1, (tm - 1) if (tm - 1) & 1 else tm - 2
-            per_pos = 0
-            for p_ in range(tm - 1):
-                x_ = 1 if p_ == 0 else (p_ + 1) // 2 + 1
-                steps_ = top_even // 2 + (top_odd - 1) // 2
-                per_pos += steps_ * (mul_small(x_ * x_) + jmadd) + mul_small(x_) + 2 * mc["jac"]
-            mads_per_proof += 2 * n * per_pos + (2 * tm - 2) * 2 * n * mc["norm"]        # + normalisation of the evaluated vectors
-        # bucket-method MSMs: one mixed addition per term and window; per (MSM, window) the wave-wide reduction on 64 lanes
-        # (XYZZ + XYZZ, 12M+2S; 13 + 2 NB - 3 of them) and the fold (c doublings + 1 addition)
-        bw = geo_own["windows"]
-        fm = mc["field"]
-        xyzz_add = 12 * fm["mul"] + 2 * fm["sqr"]
-        for terms_k, jobs_k, geo in (("bucket_terms", "bucket_jobs", geo_own), ("group_terms", "group_jobs", geo_grp)):
-            if geo:
-                mads_per_proof += stats.get(terms_k, 0) * geo["windows"] * mc["madd"]
-                mads_per_proof += stats.get(jobs_k, 0) * geo["windows"] * (geo["reduction_adds"] * 64 * xyzz_add + geo["bits"] * mc["dbl"] + mc["jac"])
-        mads = mads_per_proof * total_proofs / world
-        int_mul = {"bound": "v_mad_u64_u32 issue", "achieved": round(mads / (kernel_ms_total * 1e-3) / 1e9, 1),
-                   "peak": INT_MAD_PEAK_G, "unit": "Gmad/s",
-                   "frac": mads / (kernel_ms_total * 1e-3) / 1e9 / INT_MAD_PEAK_G,
-                   "mads_per_proof": int(mads_per_proof), "mads_per_op": {k: v for k, v in mc.items() if k not in ("field", "a1", "issue")},
-                   "plan_stats": stats, "bucket_windows": (geo_grp or geo_own)["windows"],
-                   "mads_per_field_op": mc["field"],
-                   "note": "32x32+64 multiply-adds (v_mad_u64_u32 + v_mad_i64_i32) counted in the gfx950 assembly of THIS build "
-                           "(mental-poker_amd/mad_counts.json, tools/gen_mad_counts.py) x static plan, over the kernel time of the WHOLE step; "
-                           "peak = 1024 SIMDs x 16 lanes/clk x 2.4 GHz (sustained in tools/microbench/roof.hip: 35.3 T/s at 2.28 GHz and 1.17 kW). "
-                           "The multiplies are ~55 % of the issue slots of the group law: the binding figure is roofline.compute"}
-    # ---- compute bound of the dominant kernel: VALU issue time.  Wave-level group operations of the kernel (static plan) x the issue
-    # cycles of one operation (4 x half-rate + 2 x full-rate VALU instructions of its main path, counted in the gfx950 ISA of this
-    # build) / 1024 SIMDs = the cycles every SIMD needs at the very least; divided by the kernel's measured time = the issue rate it
-    # sustained, against the shader clock (2.4 GHz maximum; the clock measured under this kernel if a PMC pass of this build exists)
-    compute = None
-    if mc and mc.get("issue"):
-        iss = mc["issue"]
-        vw, fw = stats["var_windows"], stats["fixed_windows"]
-        ops = None                      # per proof pair (prove + verify launches of one step), lane level
-        if dom_name == "k_var_msm":
-            # (chain32 with chain verification: the verifier's equation runs on the bucket kernel, only the prover uses k_var_msm)
-            sides = ("prove",) if (workload == "chain32" and not args.per_link_verify) else ("prove", "verify")
-            ops = {"madd": sum(stats[s_]["var_terms"] for s_ in sides) * vw,
-                   "dbl": sum(stats[s_]["var_jobs"] for s_ in sides) * (vw - 1) * 5}
-        elif dom_name == "k_fixed_msm":
-            ops = {"madd": sum(stats[s_]["fixed_terms"] for s_ in ("prove", "verify")) * fw - N * (fw - 1)}
-        elif dom_name == "k_remask":
-            ops = {"madd": 2 * N * (fw + 1)}
-        elif dom_name in ("k_bucket_msm", "k_bucket_acc") and "xadd" in iss:
-            if workload == "chain32" and not args.per_link_verify:
-                L_, lc_ = args.players, extras["chain_links_per_equation"]
-                nsub_ = (L_ + lc_ - 1) // lc_
-                kc_ = (lc_ + 1) * 2 * N + lc_ * (11 * m + 7) + 1
-                parts_ = [(nsub_ * kc_ / L_, nsub_ / (chain_G * L_), bucket_geometry(chain_G * kc_))]
-            else:
-                parts_ = [(stats.get("bucket_terms", 0), stats.get("bucket_jobs", 0), geo_own)]
-                if geo_grp:
-                    parts_.append((stats["group_terms"], stats["group_jobs"], geo_grp))
-            # one mixed addition per term and window (64 lanes share a window's terms evenly at best); per (MSM, window) the wave-wide
-            # reduction is 13 + 2 NB - 3 full additions on all 64 lanes
-            ops = {"madd": sum(t_ * g_["windows"] for t_, j_, g_ in parts_), "xadd": sum(j_ * g_["windows"] * g_["reduction_adds"] * 64 for t_, j_, g_ in parts_)}
-        if ops and sum(ops.values()) > 0:       # (plan_stats describes the throughput plan: small batches on the finer splits have no entry)
-            cyc_per_proof = sum(ops[k] * iss[k]["cycles"] for k in ops)                     # lane-level issue cycles x 1 lane
-            waves_cycles = cyc_per_proof * (total_proofs / world) / 64.0                        # wave-level instructions issue for 64 lanes at once
-            achieved_ghz = waves_cycles / SIMDS / (dom_ms * 1e-3) / 1e9
-            # second view, the one the SQ counters see: every VALU instruction takes one 4-cycle issue slot of its SIMD (in streams that
-            # mix the two classes the cheap instructions do not get their 2-cycle rate: roof microbenchmark, mad:cheap rows)
-            insts_per_proof = sum(ops[k] * (iss[k]["half_rate"] + iss[k]["full_rate"]) for k in ops)
-            slot_ginst = insts_per_proof * (total_proofs / world) / 64.0 / (dom_ms * 1e-3) / 1e9
-            slots = {"valu_insts_per_op": {k: iss[k]["half_rate"] + iss[k]["full_rate"] for k in ops},
-                     "achieved_G_wave_insts_per_s": round(slot_ginst, 2), "peak_G_wave_insts_per_s": SIMDS * CLK_MAX_GHZ / 4.0,
-                     "frac": slot_ginst / (SIMDS * CLK_MAX_GHZ / 4.0), "frac_at_measured_clock": None,
-                     "note": "one VALU instruction per 4-cycle slot per SIMD; static instruction counts x plan"}
-            compute = {"bound": "valu_issue", "kernel": dom_name, "achieved": round(achieved_ghz, 4), "peak": CLK_MAX_GHZ,
-                       "unit": "G issue-cycles/s per SIMD (= GHz of fully used VALU issue port)", "frac": achieved_ghz / CLK_MAX_GHZ,
-                       "ops_per_proof": {k: round(v, 1) for k, v in ops.items()},
-                       "issue_cycles_per_op": {k: iss[k] for k in ops},
-                       "clock_mhz": None, "peak_at_measured_clock": None, "frac_at_measured_clock": None, "issue_slots": slots,
-                       "note": "ideal issue time = sum over wave-level operations of (4 x half-rate + 2 x full-rate VALU instructions) / 1024 "
-                               "SIMDs; instruction counts from the gfx950 ISA of this build (mad_counts.json: valu_issue), classes and "
-                               "the no-co-issue rule from tools/microbench/roof.hip (profiles/r03_roof.json)"}
-    # HBM traffic of the dominant kernel: PMC pass (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs, gfx950 x2
-    # correction applied to FETCH_SIZE) of THIS build at THIS configuration, if one is committed under profiles/
-    src_hash = engine_source_hash()
-    traffic, traffic_src = None, None
-    pmc_path, pmc = find_pmc_summary(src_hash, curve, m, n, B, workload)
-    if pmc and dom_name in pmc.get("kernels", {}):
-        e_ = pmc["kernels"][dom_name]
-        traffic = e_.get("hbm_bytes_per_proof_per_step", e_["hbm_bytes_per_proof_per_step_corrected"]) * (total_proofs / world) / dom_count
-        traffic_src = pmc_path
-        if compute and e_.get("clock_mhz"):
-            # effective shader clock under this kernel = GRBM_GUI_ACTIVE / 8 XCDs / dispatch duration, both of the SAME profiled pass
-            compute["clock_mhz"] = round(e_["clock_mhz"], 1)
-            compute["peak_at_measured_clock"] = round(e_["clock_mhz"] / 1e3, 4)
-            compute["frac_at_measured_clock"] = min(1.0, compute["achieved"] / (e_["clock_mhz"] / 1e3))
-            compute["clock_source"] = pmc_path
-            compute["issue_slots"]["frac_at_measured_clock"] = min(1.0, compute["issue_slots"]["achieved_G_wave_insts_per_s"] / (SIMDS * e_["clock_mhz"] / 1e3 / 4.0))
-        if compute and e_.get("SQ_INSTS_VALU_per_launch"):
-            compute["valu_insts_per_launch_pmc"] = e_["SQ_INSTS_VALU_per_launch"]
-            # measured, not modelled: SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x shader cycles of the dispatch), same PMC pass
-            compute["issue_slots"]["measured_pmc"] = e_.get("valu_slot_utilisation")
-    roofline = {
-        "bound": "hbm", "kernel": dom_name, "achieved": round(achieved_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-        "avg_launch_ms": dom_ms / dom_count, "launches": dom_count,
-        "alg_bytes_per_launch": dom_bytes / dom_count, "alg_bytes_per_proof": per_proof,
-        "note": "path is bound by VALU issue, not by HBM (SURVEY 8d3): see compute (dominant kernel) and int_mul (whole step)",
-        "compute": compute,
-        "int_mul": int_mul,
-        "whole_path_hbm_frac": value / world * whole_path_bytes / 1e9 / HBM_PEAK_GBS,
-        "kernels_ms": {k: round(v[1], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
-        "kernel_launches": {k: v[0] for k, v in prof.items()}, "priming_launches": priming_launches,
-        "engine_src": src_hash,
-    }
-
-    # one row per kernel that takes >= 3 % of the step: per-launch time, algorithmic bytes per launch and their fraction of the HBM peak,
-    # and -- from the PMC pass of THIS build at THIS configuration, if one is committed under profiles/ -- the VALU issue slots it used,
-    # its clock and the bytes the counters saw per launch
-    rows_k = []
-    for k_, (cnt_, ms_) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
-        if ms_ < 0.03 * kernel_ms_total or not cnt_:
-            continue
-        ab = alg_bytes_per_proof(k_)
-        row = {"kernel": k_, "share": round(ms_ / kernel_ms_total, 4), "ms": round(ms_ / cnt_, 3), "launches_per_step": round(cnt_ / args.steps, 2),
-               "alg_bytes": None if ab is None else int(ab * total_proofs / world / cnt_),
-               "hbm_frac": None if ab is None else round(ab * total_proofs / world / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-               "valu_slots": None, "clock_mhz": None, "pmc_bytes": None}
-        e_ = (pmc or {}).get("kernels", {}).get(k_) if pmc else None
-        if e_:
-            row["valu_slots"] = e_.get("valu_slot_utilisation")
-            row["clock_mhz"] = e_.get("clock_mhz")
-            pb_ = e_.get("hbm_bytes_per_proof_per_step", e_.get("hbm_bytes_per_proof_per_step_corrected"))
-            row["pmc_bytes"] = None if pb_ is None else int(pb_ * (total_proofs / world) / cnt_)
-        rows_k.append(row)
-    roofline["kernels"] = rows_k
-    roofline["kernels_pmc_source"] = pmc_path if pmc else None
+            ab = alg_bytes_per_proof(k_)
+            row = {"kernel": k_, "share": round(ms_ / kernel_ms_total, 4), "ms": round(ms_ / cnt_, 3), "launches_per_step": round(cnt_ / args.steps, 2),
+                   "alg_bytes": None if ab is None else int(ab * total_proofs / world / cnt_),
+                   "hbm_frac": None if ab is None else round(ab * total_proofs / world / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                   "valu_slots": None, "clock_mhz": None, "pmc_bytes": None}
+            e_ = (pmc or {}).get("kernels", {}).get(k_) if pmc else None
+            if e_:
+                row["valu_slots"] = e_.get("valu_slot_utilisation")
+                row["clock_mhz"] = e_.get("clock_mhz")
+                pb_ = e_.get("hbm_bytes_per_proof_per_step", e_.get("hbm_bytes_per_proof_per_step_corrected"))
+                row["pmc_bytes"] = None if pb_ is None else int(pb_ * (total_proofs / world) / cnt_)
+            rows_k.append(row)
+        roofline["kernels"] = rows_k
+        roofline["kernels_pmc_source"] = pmc_path if pmc else None
 
     # ---- CPU baseline: the oracle's C++ restatement (port), single thread, bounded sample
     cpu = None
-    if not args.no_cpu_baseline:                  # rank 0 only (the other ranks have returned); N > 1 lines carry it too
+    if args.full and not args.no_cpu_baseline:    # rank 0 only (the other ranks have returned); N > 1 lines carry it too
         import coracle as co
         numa = pin_to_gpu_numa_node(local)        # the host cores next to this rank's GPU
         it = args.cpu_iters if N <= 64 else max(2, args.cpu_iters * 52 // (N * max(1, m // 2)))
@@ -1238,7 +1313,7 @@ def main():
 
     # ---- the same device-resident step on a table from plain mp_table_create (the call INTEGRATION.md's Rust `table_for` makes): the
     # engine sizes the fixed-base windows by the HBM that is free.  Last, because the benchmarked table has to go first.
-    if workload == "pairs" and world == 1 and not args.no_extras and args.keyed == 0 and not args.per_equation and S == 1 and not args.pipeline:
+    if args.full and workload == "pairs" and world == 1 and not args.no_extras and args.keyed == 0 and not args.per_equation and S == 1 and not args.pipeline:
         table.close()
         del tables[:]
         torch.cuda.empty_cache()
@@ -1283,6 +1358,7 @@ def main():
               "rccl_smoke": smoke_log, "pipeline_depth": args.pipeline,
               "subgroup_check": (not args.no_subgroup_check) if curve == "bls12_377" else None,
               "validated_once": bool(args.validated_once),
+              "full": bool(args.full),
               "table_build_s": round(table_build_s, 3),
               "hbm_per_rank_gb": hbm_used_gb,
               "per_rank_proofs": [int(r[0]) for r in rows], "per_rank_failed": [int(r[1]) for r in rows],

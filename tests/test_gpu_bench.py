@@ -1,7 +1,8 @@
 """GPU tests of bench.py itself (run on the MI355X box): `--gpus N` started from a plain shell launches N ranks on its own,
 the sharded run produces byte-identical outputs to an unsharded run of the same proofs, and the JSON line carries what the
 driver reads.  The box has one GPU: MP_BENCH_FORCE_DEVICE / MP_BENCH_BACKEND=gloo put both ranks on it and run the
-once-per-session collectives over gloo (on an 8-GPU node the same code path uses RCCL)."""
+once-per-session collectives over gloo (on an 8-GPU node the same code path uses RCCL).  What the line carries beside the headline
+(oracle parity, roofline, telemetry, extras, cpu_baseline) needs `--full`; a plain run times the steps and can dump its outputs."""
 import json
 import os
 import subprocess
@@ -35,7 +36,7 @@ def _telemetry_keys(c, world):
         assert (f is None or 100 < f < 3000) and (p_ is None or 10 < p_ < 2000) and n_ >= 0
 
 
-COMMON = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--fb-bits", "8", "--digest", "--seed-block", "192"]
+COMMON = ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--fb-bits", "8", "--digest", "--seed-block", "192"]
 
 
 def test_self_launch_two_ranks_equals_unsharded():
@@ -66,7 +67,7 @@ def test_strong_scaling_two_ranks_equals_unsharded():
 
 
 def test_json_line_contract_and_extras():
-    d = run_bench("--batch", "16384", "--steps", "2", "--warmup", "1", "--fb-bits", "8", "--cpu-iters", "2")      # (throughput plan: > 14 336 proofs)
+    d = run_bench("--full", "--batch", "16384", "--steps", "2", "--warmup", "1", "--fb-bits", "8", "--cpu-iters", "2")      # (throughput plan: > 14 336 proofs)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d
@@ -97,7 +98,7 @@ def test_json_line_contract_and_extras():
 def test_batch_curve_on_the_line():
     """config.batch_curve: proofs/s with 1 024 .. 32 768 proofs in flight, serial and with the verify calls pipelined, measured after the
     timed region on the benchmarked table"""
-    d = run_bench("--batch", "32768", "--steps", "1", "--warmup", "1", "--fb-bits", "16", "--no-cpu-baseline")
+    d = run_bench("--full", "--batch", "32768", "--steps", "1", "--warmup", "1", "--fb-bits", "16", "--no-cpu-baseline")
     bc = d["config"]["batch_curve"]
     assert sorted(bc, key=int) == ["1024", "4096", "16384", "32768"]
     for k, v in bc.items():
@@ -110,7 +111,7 @@ def test_batch_curve_on_the_line():
                                             ("chain32", ["--batch", "256", "--players", "4", "--chain-slice", "96", "--chain-group", "4"]),
                                             ("mixed", ["--batch", "512"])])
 def test_workload_modes(workload, extra):
-    d = run_bench("--workload", workload, "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--fb-bits", "8", *extra)
+    d = run_bench("--full", "--workload", workload, "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--fb-bits", "8", *extra)
     assert d["config"]["workload"].startswith(workload) and d["config"]["parity_vs_oracle"] is True and d["value"] > 0
     if workload == "mixed":
         assert "secp256k1" in d["config"]["workload"]
@@ -122,7 +123,7 @@ def test_workload_modes(workload, extra):
 def test_two_ranks_other_workloads(workload, extra, per_rank):
     """config 3 (32 dependent shuffles per table, one chain equation per table) and config 5 (mixed prove / verify stream on secp256k1)
     through the N > 1 path: two self-launched ranks, every proof accepted on both, the N > 1 line keeps cpu_baseline and roofline"""
-    d = run_bench("--gpus", "2", "--workload", workload, "--steps", "1", "--warmup", "1", "--fb-bits", "8", "--cpu-iters", "2", *extra,
+    d = run_bench("--full", "--gpus", "2", "--workload", workload, "--steps", "1", "--warmup", "1", "--fb-bits", "8", "--cpu-iters", "2", *extra,
                   env={"MP_BENCH_FORCE_DEVICE": "0", "MP_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["config"]["rccl_world"] == 2 and d["config"]["collective_backend"] == "gloo"
     assert d["config"]["per_rank_proofs"] == [per_rank, per_rank] and d["config"]["per_rank_failed"] == [0, 0]
@@ -147,3 +148,41 @@ def test_eight_ranks_weak_and_strong_equal_unsharded():
         assert c["rccl_smoke"]["rccl_world"] == 8 and c["parity_vs_oracle"] is True
         flat = [x for per_rank in c["digests"] for x in per_rank]
         assert flat == single["config"]["digests"][0] and len(flat) == 8 and len(set(flat)) == 8
+
+
+def _dumped(d):
+    import numpy as np
+    files = sorted(os.listdir(d))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 * 10**6
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    return out
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run times --steps steps and prints the headline with nothing measured beside it; --dump-outputs writes the last timed
+    step's outputs, and a --full run of the same arguments (which also checks a timed proof against the oracle) writes the same ones"""
+    import numpy as np
+    args = ["--batch", "512", "--steps", "3", "--warmup", "1", "--fb-bits", "8"]
+    plain = run_bench(*args, "--dump-outputs", str(tmp_path / "plain"))
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["n_gpus"] == 1
+    assert plain["metric"] == "shuffle proofs/sec (prove+verify)" and plain["unit"] == "proofs/s" and plain["higher_is_better"] is True
+    assert abs(plain["value"] - 512 / (plain["ms_per_step"] * 1e-3)) < 1e-6 * plain["value"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["config"]["parity_vs_oracle"] is None
+    assert plain["config"]["full"] is False and "per_equation_value" not in plain["config"]
+    full = run_bench(*args, "--full", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / "full"))
+    assert full["config"]["parity_vs_oracle"] is True and full["roofline"]["kernel"].startswith("k_")
+    a, b = _dumped(tmp_path / "plain"), _dumped(tmp_path / "full")
+    assert sorted(a) == ["proofs", "prove_status", "rows", "shuffled_decks", "verify_status"]
+    assert a["shuffled_decks"].shape == (512, 52 * 128) and a["proofs"].shape[0] == 512
+    assert not a["prove_status"].any() and not a["verify_status"].any()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_chain_workload_dumps_every_link(tmp_path):
+    d = run_bench("--workload", "chain32", "--batch", "256", "--players", "4", "--steps", "1", "--warmup", "1", "--fb-bits", "8",
+                  "--dump-outputs", str(tmp_path))
+    out = _dumped(tmp_path)
+    assert d["roofline"] is None and out["shuffled_decks"].shape == (4 * 256, 52 * 128) and out["proofs"].shape[0] == 4 * 256
+    assert not out["prove_status"].any() and not out["verify_status"].any()

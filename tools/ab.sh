@@ -9,7 +9,7 @@ set -e
 for round in 1 2; do
   for v in "$@"; do
     cp tools/ab/lib_$v.so mental-poker_amd/libmpshuffle.so
-    python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = d['roofline']['kernels_ms']
 print('%-10s %7d proofs/s %7.1f ms/step  var %.1f  table %.1f  fixed %.1f  remask %.1f' % (sys.argv[1], d['value'], d['ms_per_step'], k['k_var_msm'], k['k_table'], k['k_fixed_msm'], k['k_remask']))" $v

@@ -1,6 +1,6 @@
 #!/bin/bash
 # BLS12-377 (row f3), 300 cards (10,30): with and without the per-point subgroup test, groups on / off, proofs in flight
-X="--no-extras --no-cpu-baseline --steps 2 --warmup 1 --curve bls12_377 --m 10 --n 30"
+X="--full --no-extras --no-cpu-baseline --steps 2 --warmup 1 --curve bls12_377 --m 10 --n 30"
 for cfg in "--batch 4096" "--batch 4096 --no-subgroup-check" "--batch 4096 --no-subgroup-check --group-points 30464" "--batch 8192 --no-subgroup-check" "--batch 8192 --no-subgroup-check --group-points 30464" "--batch 16384 --no-subgroup-check --group-points 30464" "--batch 16384"; do
   echo "== $cfg"
   timeout 900 python bench.py $X $cfg 2>&1 | python -c "

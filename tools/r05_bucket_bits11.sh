@@ -1,4 +1,4 @@
-X="--no-extras --no-cpu-baseline --steps 3 --warmup 1"
+X="--full --no-extras --no-cpu-baseline --steps 3 --warmup 1"
 for cfg in "" "--bucket-bits 11" "--workload chain32" "--workload chain32 --bucket-bits 11" "--workload chain32 --chain-group 12 --chain-slice 21504" "" "--bucket-bits 11"; do
   echo "== $cfg"
   python bench.py $X $cfg 2>/dev/null | python -c "

@@ -6,7 +6,7 @@ for cfg in "$@"; do
   set -- $cfg
   T=$1; LK=$2; shift 2
   echo "== tables $T, links per chain equation $LK $*"
-  timeout 600 python bench.py --workload chain32 --batch $T --chain-max-links $LK --steps 2 --warmup 1 --no-cpu-baseline "$@" 2>&1 | python -c "
+  timeout 600 python bench.py --full --workload chain32 --batch $T --chain-max-links $LK --steps 2 --warmup 1 --no-cpu-baseline "$@" 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     line = line.strip()
