@@ -37,6 +37,11 @@
  *     another thread until the call has returned (pipelined verification, mp_set_pipeline: until mp_sync or `depth` further verify
  *     calls have), and no call is in flight on a context or table that is being destroyed.  The library reads no environment variable
  *     and keeps no mutable global.  tests/test_gpu_round6.py::test_four_host_threads_* and tests/test_threads_tsan.py hold it to that.
+ *     Coalescing (mp_set_coalesce, off by default): the single-proof calls of several threads on one table are gathered into batched
+ *     calls; a thread still gets only its own outputs, status word and mp_last_error.  mp_set_coalesce applies to the batches opened
+ *     after it -- a batch already open completes under the settings it opened with -- and may be called at any time, also while
+ *     calls are queued.  mp_table_destroy while single-proof calls are queued or in flight on that table is the caller's error, as for
+ *     every other call.  tests/test_coalesce_tsan.py and tests/test_gpu_coalesce.py hold it to that.
  */
 #ifndef MPSHUFFLE_H
 #define MPSHUFFLE_H
@@ -117,6 +122,28 @@ int mp_shuffle_and_remask(mp_table* t, const uint8_t* deck, const uint8_t* maski
                           uint8_t* out_proof);
 int mp_verify_shuffle(mp_table* t, const uint8_t* deck, const uint8_t* shuffled_deck, const uint8_t* proof,
                       size_t proof_len);
+/* the same with the aggregate key given per call, as the reference passes `shared_key` [REF mod.rs:380-386, 420-426]: valid on keyless
+ * tables (mp_table_create_params) and on keyed ones, whose own key it overrides for this call.  Bytes and status words are those of
+ * mp_shuffle_and_remask / mp_verify_shuffle on a table created with that key. */
+int mp_shuffle_and_remask_keyed(mp_table* t, const uint8_t* shared_key, const uint8_t* deck, const uint8_t* masking_factors,
+                                const uint32_t* permutation, const uint8_t prover_seed[32], uint8_t* out_deck, uint8_t* out_proof);
+int mp_verify_shuffle_keyed(mp_table* t, const uint8_t* shared_key, const uint8_t* deck, const uint8_t* shuffled_deck,
+                            const uint8_t* proof, size_t proof_len);
+/* Coalescing of the four single-proof entry points above (off by default: every call is a batch of one).  A server with many
+ * concurrent single-proof requests sets it on ONE table (a keyless one with the _keyed calls, when its card tables differ by key):
+ * the calls that arrive while the context is busy are gathered and each gathering is ONE batched call (mp_*_batch / mp_*_batch_keys),
+ * so T threads share the throughput of a batch of ~T proofs instead of running T batches of one.  Four queues per table -- prove and
+ * verify, each with and without a per-call key -- that never mix.  A batch closes when it holds max_batch requests (1 .. 65 536), or
+ * when its first caller holds the context's lock and max_wait_us have passed since it opened (0: a lone caller on an idle context
+ * waits for nothing; while an earlier batch runs, the next one fills by itself).  Every caller packs its own inputs into page-locked
+ * staging (two sets of max_batch requests per queue in use) and copies its own outputs back.  Status words go to their own caller
+ * only; if a batched call fails as a whole (< 0), its requests are run again one by one, so every caller gets exactly what its
+ * uncoalesced call returns.  max_batch = 0 switches it off.  The _batch and _dev entry points are never coalesced. */
+int mp_set_coalesce(mp_table* t, size_t max_batch, uint32_t max_wait_us);
+/* counters since the last mp_set_coalesce: out[0] requests served, [1] batched calls run, [2] largest batch, [3] batches closed full,
+ * [4] batches closed by time, [5] requests re-run one by one after a failed batched call, [6] summed queue wait (arrival to the start
+ * of its batched call) in microseconds, [7] reserved (0) */
+int mp_coalesce_stats(const mp_table* t, uint64_t out[8]);
 
 /* ---- batched forms: B independent proofs, arrays of the single-proof buffers back to back -------------------
  * status[b] receives the per-proof result; the return value is < 0 only for call-level errors. */

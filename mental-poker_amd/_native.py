@@ -20,6 +20,7 @@ SYMBOLS = [
     "mp_verify_shuffle_batch_keys", "mp_shuffle_and_remask_batch_keys_dev", "mp_verify_shuffle_batch_keys_dev",
     "mp_keyset_create", "mp_keyset_destroy", "mp_keyset_size", "mp_shuffle_and_remask_batch_keyset_dev", "mp_verify_shuffle_batch_keyset_dev",
     "mp_setup", "mp_table_create", "mp_table_create_ex", "mp_table_window_bits", "mp_table_destroy", "mp_shuffle_and_remask", "mp_verify_shuffle",
+    "mp_shuffle_and_remask_keyed", "mp_verify_shuffle_keyed", "mp_set_coalesce", "mp_coalesce_stats",
     "mp_shuffle_and_remask_batch", "mp_verify_shuffle_batch", "mp_shuffle_and_remask_batch_dev",
     "mp_verify_shuffle_batch_dev", "mp_verify_shuffle_chain", "mp_verify_shuffle_chain_dev", "mp_sync", "mp_reserve", "mp_set_latency_batch", "mp_remask_batch", "mp_msm", "mp_commit_batch",
     "mp_profile_enable", "mp_profile_report", "mp_work_census", "mp_plan_stats", "mp_sigma_prove_batch",
@@ -169,6 +170,10 @@ def bind(cdll):
     cdll.mp_table_destroy.restype = None
     cdll.mp_shuffle_and_remask.argtypes = [c.c_void_p, u8p, u8p, u32p, u8p, u8p, u8p]
     cdll.mp_verify_shuffle.argtypes = [c.c_void_p, u8p, u8p, u8p, c.c_size_t]
+    cdll.mp_shuffle_and_remask_keyed.argtypes = [c.c_void_p, u8p, u8p, u8p, u32p, u8p, u8p, u8p]
+    cdll.mp_verify_shuffle_keyed.argtypes = [c.c_void_p, u8p, u8p, u8p, u8p, c.c_size_t]
+    cdll.mp_set_coalesce.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32]
+    cdll.mp_coalesce_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
     cdll.mp_shuffle_and_remask_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_verify_shuffle_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, i32p]
     cdll.mp_shuffle_and_remask_batch_dev.argtypes = [c.c_void_p, c.c_size_t] + [c.c_void_p] * 7
@@ -549,6 +554,40 @@ class Table:
         self._need("proof", len(proof), self.proof_bytes)
         rc = self.lib.mp_verify_shuffle(self.h, _in(deck), _in(shuffled), _in(proof), len(proof))
         return self.eng._chk(rc)
+
+    # ---- single proofs with the aggregate key given per call (keyless tables included); coalesced when set_coalesce is on
+    def shuffle_and_remask_keyed(self, shared_key, deck, factors, perm, seed):
+        self._need("shared key", len(shared_key), self.pb)
+        self._need("deck", len(deck), self.N * self.cb)
+        self._need("masking factors", len(factors), self.N * 32)
+        self._need("permutation", len(perm), self.N)
+        self._need("prover seed", len(seed), 32)
+        out_d = (ctypes.c_uint8 * (self.N * self.cb))()
+        out_p = (ctypes.c_uint8 * self.proof_bytes)()
+        pm = (ctypes.c_uint32 * self.N)(*perm)
+        rc = self.lib.mp_shuffle_and_remask_keyed(self.h, _in(shared_key), _in(deck), _in(factors), pm, _in(seed), out_d, out_p)
+        self.eng._chk(rc)
+        return bytes(out_d), bytes(out_p)
+
+    def verify_shuffle_keyed(self, shared_key, deck, shuffled, proof):
+        self._need("shared key", len(shared_key), self.pb)
+        self._need("deck", len(deck), self.N * self.cb)
+        self._need("shuffled deck", len(shuffled), self.N * self.cb)
+        self._need("proof", len(proof), self.proof_bytes)
+        rc = self.lib.mp_verify_shuffle_keyed(self.h, _in(shared_key), _in(deck), _in(shuffled), _in(proof), len(proof))
+        return self.eng._chk(rc)
+
+    def set_coalesce(self, max_batch, max_wait_us=0):
+        """gather the concurrent single-proof calls of this table (shuffle_and_remask, verify_shuffle and their _keyed forms) into batched
+        calls of up to max_batch requests; a batch waits at most max_wait_us for more once the context is free; max_batch = 0: off"""
+        self.eng._chk(self.lib.mp_set_coalesce(self.h, int(max_batch), int(max_wait_us)))
+
+    def coalesce_stats(self):
+        """counters since set_coalesce"""
+        v = (ctypes.c_uint64 * 8)()
+        self.eng._chk(self.lib.mp_coalesce_stats(self.h, v))
+        keys = ["served", "batches", "largest", "closed_full", "closed_time", "rerun", "wait_us"]
+        return dict(zip(keys, [int(x) for x in v[:7]]))
 
     def remask_batch(self, cards, factors):
         count = len(cards) // self.cb

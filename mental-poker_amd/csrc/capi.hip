@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "engine_base.hpp"
+#include "coalesce.hpp"
 
 namespace mp {
 std::string& last_error() {
@@ -230,6 +231,7 @@ int mp_table_create_ex(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* param
     delete t;
     return rc;
   }
+  t->co = new mp_coalescer();
   ctx->tables.push_back(t);
   *out = t;
   return MP_OK;
@@ -259,6 +261,7 @@ void mp_table_destroy(mp_table* t) {
       if (st.done) rt::event_destroy(st.done);
       if (st.down) rt::event_destroy(st.down);
     }
+    delete t->co;
     delete t;
     last = ctx->dying && reg.empty();
   }
@@ -274,7 +277,11 @@ void* mp_host_alloc(size_t bytes) {
 }
 void mp_host_free(void* p) { rt::host_free(p); }
 
-uint32_t mp_table_window_bits(const mp_table* t) { return t ? t->fb_bits : 0; }
+uint32_t mp_table_window_bits(const mp_table* t) {
+  if (!t) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
+  return t->fb_bits;
+}
 int mp_set_latency_batch(mp_table* t, size_t B) {
   if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_latency_batch: null table");
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
@@ -300,7 +307,11 @@ int mp_set_group_refine(mp_table* t, uint32_t points_per_subgroup, uint32_t min_
   t->set_group_refine(points_per_subgroup, min_subgroups);
   return MP_OK;
 }
-uint64_t mp_reverified_count(const mp_table* t) { return t ? t->reverified() : 0; }
+uint64_t mp_reverified_count(const mp_table* t) {
+  if (!t) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (a verify call on another thread writes it)
+  return t->reverified();
+}
 int mp_set_group_adapt(mp_table* t, int on) {
   if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_group_adapt: null table");
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
@@ -402,9 +413,14 @@ int mp_set_group_verify(mp_table* t, uint32_t points_per_group, size_t min_batch
   return MP_OK;
   MP_CATCH
 }
-uint32_t mp_group_size(const mp_table* t, size_t B) { return t ? t->group_size_of(B) : 0; }
+uint32_t mp_group_size(const mp_table* t, size_t B) {
+  if (!t) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (the group adaptation of a verify call on another thread writes it)
+  return t->group_size_of(B);
+}
 uint32_t mp_chain_group_size(const mp_table* t, size_t tables, uint32_t links, int keyed) {
   if (!t || !tables || !links) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
   // (as mp_verify_shuffle_chain_dev cuts the chain: the sub-chains of a long chain are equations of their own)
   const size_t per_link = (size_t)2 * t->N + 11 * t->m + 8, fixed_part = (size_t)2 * t->N + 1;
   const size_t eq_cap = fixed_part + per_link > 32767 ? (size_t)65535 : 32767;
@@ -413,7 +429,11 @@ uint32_t mp_chain_group_size(const mp_table* t, size_t tables, uint32_t links, i
   if (t->chain_max_links) lmax = std::max(1u, std::min(lmax, t->chain_max_links));
   return t->chain_group_size(tables, std::min(lmax, links), keyed != 0);
 }
-size_t mp_chain_last_slice(const mp_table* t) { return t ? t->chain_last_slice : 0; }
+size_t mp_chain_last_slice(const mp_table* t) {
+  if (!t) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
+  return t->chain_last_slice;
+}
 int mp_set_pipeline(mp_table* t, int depth) {
   if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_pipeline: null table");
   MP_TRY
@@ -861,22 +881,105 @@ int mp_verify_shuffle_batch_keys(mp_table* t, size_t B, const uint8_t* shared_ke
   if (!shared_keys) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_batch_keys: null keys");
   return verify_batch_host(t, B, shared_keys, decks, shuffled_decks, proofs, status);
 }
-int mp_shuffle_and_remask(mp_table* t, const uint8_t* deck, const uint8_t* masking_factors, const uint32_t* permutation,
-                          const uint8_t prover_seed[32], uint8_t* out_deck, uint8_t* out_proof) {
+// ---- single-proof entry points: one proof per call, as the reference's trait [REF src/lib.rs:181-197].  With coalescing on
+// (mp_set_coalesce) the concurrent calls of a table are gathered into batched calls (coalesce.hpp); off, a call is a batch of one.
+static int single_prove(mp_table* t, const uint8_t* key, const uint8_t* deck, const uint8_t* masking_factors, const uint32_t* permutation,
+                        const uint8_t* prover_seed, uint8_t* out_deck, uint8_t* out_proof) {
   int32_t st = 0;
-  int rc = mp_shuffle_and_remask_batch(t, 1, deck, masking_factors, permutation, prover_seed, out_deck, out_proof, &st);
+  int rc = 1;
+  // (arguments that fail the batched call's checks go the uncoalesced way: same checks, same codes)
+  if (t && co_on(t) && deck && masking_factors && permutation && prover_seed && out_deck && out_proof && (key || !t->keyless)) {
+    MP_TRY
+    CoRequest r;
+    r.key = key;
+    r.deck = deck;
+    r.rho = masking_factors;
+    r.perm = permutation;
+    r.seed = prover_seed;
+    r.out_deck = out_deck;
+    r.out_proof = out_proof;
+    const CoGeom g = co_geom(t, key ? CO_PROVE_KEYED : CO_PROVE);
+    rc = co_submit(t, key ? CO_PROVE_KEYED : CO_PROVE, r, [&](CoSet& s, size_t f, size_t c) {
+      return prove_batch_host(t, c, key ? s.keys + f * g.pb : nullptr, s.decks + f * g.dsz, s.rho + f * g.N * 32, s.perm + f * g.N,
+                              s.seeds + f * 32, s.out_decks + f * g.dsz, s.out_proofs + f * g.psz, s.status + f);
+    }, &st);
+    MP_CATCH
+  }
+  if (rc == 1) rc = prove_batch_host(t, 1, key, deck, masking_factors, permutation, prover_seed, out_deck, out_proof, &st);
   if (rc != MP_OK) return rc;
   if (st < 0) return fail(st, mp_check_name(st));
   return st;
 }
-int mp_verify_shuffle(mp_table* t, const uint8_t* deck, const uint8_t* shuffled_deck, const uint8_t* proof, size_t proof_len) {
+static int single_verify(mp_table* t, const uint8_t* key, const uint8_t* deck, const uint8_t* shuffled_deck, const uint8_t* proof,
+                         size_t proof_len) {
   if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle: null table");
   if (proof_len != proof_size_bytes(t->m, t->n, t->point_bytes)) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle: wrong proof length");
   int32_t st = 0;
-  int rc = mp_verify_shuffle_batch(t, 1, deck, shuffled_deck, proof, &st);
+  int rc = 1;
+  if (co_on(t) && deck && shuffled_deck && proof && (key || !t->keyless)) {
+    MP_TRY
+    CoRequest r;
+    r.key = key;
+    r.deck = deck;
+    r.shuf = shuffled_deck;
+    r.proof = proof;
+    const CoGeom g = co_geom(t, key ? CO_VERIFY_KEYED : CO_VERIFY);
+    rc = co_submit(t, key ? CO_VERIFY_KEYED : CO_VERIFY, r, [&](CoSet& s, size_t f, size_t c) {
+      return verify_batch_host(t, c, key ? s.keys + f * g.pb : nullptr, s.decks + f * g.dsz, s.shuf + f * g.dsz, s.proofs + f * g.psz,
+                               s.status + f);
+    }, &st);
+    MP_CATCH
+  }
+  if (rc == 1) rc = verify_batch_host(t, 1, key, deck, shuffled_deck, proof, &st);
   if (rc != MP_OK) return rc;
   if (st < 0) return fail(st, mp_check_name(st));
   return st;
+}
+int mp_shuffle_and_remask(mp_table* t, const uint8_t* deck, const uint8_t* masking_factors, const uint32_t* permutation,
+                          const uint8_t prover_seed[32], uint8_t* out_deck, uint8_t* out_proof) {
+  return single_prove(t, nullptr, deck, masking_factors, permutation, prover_seed, out_deck, out_proof);
+}
+int mp_verify_shuffle(mp_table* t, const uint8_t* deck, const uint8_t* shuffled_deck, const uint8_t* proof, size_t proof_len) {
+  return single_verify(t, nullptr, deck, shuffled_deck, proof, proof_len);
+}
+int mp_shuffle_and_remask_keyed(mp_table* t, const uint8_t* shared_key, const uint8_t* deck, const uint8_t* masking_factors,
+                                const uint32_t* permutation, const uint8_t prover_seed[32], uint8_t* out_deck, uint8_t* out_proof) {
+  if (!shared_key) return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_keyed: null key");
+  return single_prove(t, shared_key, deck, masking_factors, permutation, prover_seed, out_deck, out_proof);
+}
+int mp_verify_shuffle_keyed(mp_table* t, const uint8_t* shared_key, const uint8_t* deck, const uint8_t* shuffled_deck, const uint8_t* proof,
+                            size_t proof_len) {
+  if (!shared_key) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_keyed: null key");
+  return single_verify(t, shared_key, deck, shuffled_deck, proof, proof_len);
+}
+int mp_set_coalesce(mp_table* t, size_t max_batch, uint32_t max_wait_us) {
+  if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_coalesce: null table");
+  if (max_batch > 65536) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_coalesce: max_batch 0 (off) .. 65 536");
+  // (the queues' own mutexes only: the setting applies to the batches opened after this call, a batch in flight completes as it is)
+  t->co->max_wait_us.store(max_wait_us);
+  t->co->max_batch.store(max_batch);
+  for (CoQueue& q : t->co->q) {
+    std::lock_guard<std::mutex> lk(q.mu);
+    q.reset();
+  }
+  return MP_OK;
+}
+int mp_coalesce_stats(const mp_table* t, uint64_t out[8]) {
+  if (!t || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_coalesce_stats: bad argument");
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (context, then queue: the order of coalesce.hpp)
+  uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (CoQueue& q : t->co->q) {
+    std::lock_guard<std::mutex> lk(q.mu);
+    v[0] += q.served;
+    v[1] += q.calls;
+    v[2] = std::max(v[2], q.largest);
+    v[3] += q.closed_full;
+    v[4] += q.closed_time;
+    v[5] += q.rerun;
+    v[6] += q.wait_us;
+  }
+  memcpy(out, v, sizeof(v));
+  return MP_OK;
 }
 
 int mp_remask_batch(mp_table* t, size_t count, const uint8_t* cards, const uint8_t* masking_factors, uint8_t* out) {

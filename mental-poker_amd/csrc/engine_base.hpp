@@ -198,8 +198,10 @@ struct mp_keyset {
   mp::DevBuf<uint32_t> FB;       // [K][windows][entries] affine points (the layout of the table context's own fixed-base tables)
   uint32_t bits = 0, windows = 0, entries = 0;
 };
+struct mp_coalescer;             // request coalescing of the single-proof host-buffer entry points (capi.hip, mp_set_coalesce)
 struct mp_table {
   mp_ctx* ctx = nullptr;
+  mp_coalescer* co = nullptr;     // created with the table by capi.hip and gone with it; off until mp_set_coalesce
   mp_io_stage io[2];
   size_t io_chunk = 0;         // proofs per pipelined chunk of the host-buffer entry points (0 = default, mp_set_io_chunk)
   uint32_t m = 0, n = 0, N = 0;

@@ -10,6 +10,7 @@ All computation happens in libmpshuffle.so (HIP, gfx950); this file only moves b
     ZKProofShuffle  bytes of length proof_size(m, n)     (shuffle::proof::Proof)
 """
 import struct
+import threading
 
 from . import _native
 
@@ -112,11 +113,22 @@ class DLCards:
     """`impl BarnettSmartProtocol for DLCards<C>` -- hot-path members only (setup, shuffle_and_remask,
     verify_shuffle and their batched forms).  One instance = one curve on one GPU."""
 
-    def __init__(self, curve="stark", device=0, fb_bits=8):
+    def __init__(self, curve="stark", device=0, fb_bits=8, coalesce=None):
         self.curve = curve
         self.fb_bits = fb_bits      # fixed-base window width of the table contexts (8: compact, 16: throughput)
         self.engine = _native.Engine(curve, device)
         self._tables = {}
+        # coalesce = (max_batch, max_wait_us): shuffle_and_remask / verify_shuffle of every aggregate key go to ONE table of the
+        # parameters per (m, n, params), through the keyed single-proof calls with coalescing on -- concurrent callers (threads) share its
+        # batches whatever their keys.  None: a table per (parameters, key), as before.
+        if coalesce is not None:
+            max_batch, max_wait_us = coalesce
+            if not 1 <= int(max_batch) <= 65536 or int(max_wait_us) < 0:
+                raise CardProtocolError.io("coalesce = (max_batch 1 .. 65536, max_wait_us >= 0)")
+            coalesce = (int(max_batch), int(max_wait_us))
+        self.coalesce = coalesce
+        self._params_tables = {}
+        self._params_lock = threading.Lock()
 
     # -- fn setup<R: Rng>(rng, m, n) -> Result<Parameters, CardProtocolError>          [REF mod.rs:105-121]
     def setup(self, rng_seed, m, n):
@@ -160,6 +172,20 @@ class DLCards:
             self._tables[key] = t
         return t
 
+    def params_table(self, pp):
+        """the coalescing table of `pp` (DLCards(coalesce=...)): parameters only, one per (m, n, params), created on first use"""
+        key = (pp.m, pp.n, pp.raw)
+        with self._params_lock:
+            t = self._params_tables.get(key)
+            if t is None:
+                try:
+                    t = _native.Table(self.engine, pp.m, pp.n, pp.raw, None, self.fb_bits)
+                    t.set_coalesce(*self.coalesce)
+                except _native.NativeError as e:
+                    raise CardProtocolError.io(str(e))
+                self._params_tables[key] = t
+        return t
+
     # -- fn shuffle_and_remask<R: Rng>(rng, pp, shared_key, deck, masking_factors, permutation)
     #        -> Result<(Vec<MaskedCard>, ZKProofShuffle), CardProtocolError>            [REF mod.rs:380-418]
     def shuffle_and_remask(self, rng_seed, pp, shared_key, deck, masking_factors, permutation):
@@ -171,10 +197,13 @@ class DLCards:
             raise CardProtocolError.io("a card is %d bytes, the shared key %d" % (cb, self.engine.point_bytes))
         if len(bytes(rng_seed)) != 32:
             raise CardProtocolError.io("the prover seed is 32 bytes")
-        t = self.table(pp, shared_key)
         try:
-            out_deck, proof = t.shuffle_and_remask(b"".join(deck), _scalar_bytes(masking_factors),
-                                                   permutation.mapping, rng_seed)
+            if self.coalesce is not None:
+                out_deck, proof = self.params_table(pp).shuffle_and_remask_keyed(bytes(shared_key), b"".join(deck), _scalar_bytes(masking_factors),
+                                                                                 permutation.mapping, rng_seed)
+            else:
+                out_deck, proof = self.table(pp, shared_key).shuffle_and_remask(b"".join(deck), _scalar_bytes(masking_factors),
+                                                                                permutation.mapping, rng_seed)
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         cb = 2 * self.engine.point_bytes
@@ -192,9 +221,11 @@ class DLCards:
             raise CardProtocolError.io("a card is %d bytes" % cb)
         if len(bytes(shared_key)) != self.engine.point_bytes or len(proof) != self.engine.proof_size(pp.m, pp.n):
             raise CardProtocolError.io("shared key / proof have the wrong length")
-        t = self.table(pp, shared_key)
         try:
-            rc = t.verify_shuffle(b"".join(original_deck), b"".join(shuffled_deck), proof)
+            if self.coalesce is not None:
+                rc = self.params_table(pp).verify_shuffle_keyed(bytes(shared_key), b"".join(original_deck), b"".join(shuffled_deck), proof)
+            else:
+                rc = self.table(pp, shared_key).verify_shuffle(b"".join(original_deck), b"".join(shuffled_deck), proof)
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         if rc != 0:
