@@ -418,16 +418,24 @@ uint32_t mp_group_size(const mp_table* t, size_t B) {
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (the group adaptation of a verify call on another thread writes it)
   return t->group_size_of(B);
 }
-uint32_t mp_chain_group_size(const mp_table* t, size_t tables, uint32_t links, int keyed) {
-  if (!t || !tables || !links) return 0;
-  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
-  // (as mp_verify_shuffle_chain_dev cuts the chain: the sub-chains of a long chain are equations of their own)
+// How a chain is cut: the links one chain equation takes at the most (0 = not even one: deck too large).  An equation holds at most
+// 32 767 distinct points ((L + 1) 2N decks + L (11m + 8) proof elements + key): longer chains are verified as consecutive sub-chains,
+// equations of their own.  One link does not always fit 32 767 points -- m = 2048, n = 2: 4N + 11m + 9 = 38 921 -- but it fits one
+// bucket job: the kernel sorts up to BUCKET_TERMS_MAX = 65 535 points per window, and 4N + 11m + 9 <= 38 921 for every table
+// mp_table_create accepts, m n <= 4096
+static uint32_t chain_links_max(const mp_table* t) {
   const size_t per_link = (size_t)2 * t->N + 11 * t->m + 8, fixed_part = (size_t)2 * t->N + 1;
   const size_t eq_cap = fixed_part + per_link > 32767 ? (size_t)65535 : 32767;
   if (fixed_part + per_link > eq_cap) return 0;
-  uint32_t lmax = std::min<uint32_t>((uint32_t)((eq_cap - fixed_part) / per_link), 1022u);
+  uint32_t lmax = std::min<uint32_t>((uint32_t)((eq_cap - fixed_part) / per_link), 1022u);      // (links 0 .. L in 10 bits of a sorted entry: kernels_bucket.hpp)
   if (t->chain_max_links) lmax = std::max(1u, std::min(lmax, t->chain_max_links));
-  return t->chain_group_size(tables, std::min(lmax, links), keyed != 0);
+  return lmax;
+}
+uint32_t mp_chain_group_size(const mp_table* t, size_t tables, uint32_t links, int keyed) {
+  if (!t || !tables || !links) return 0;
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
+  const uint32_t lmax = chain_links_max(t);      // (as mp_verify_shuffle_chain_dev cuts the chain)
+  return lmax ? t->chain_group_size(tables, std::min(lmax, links), keyed != 0) : 0;
 }
 size_t mp_chain_last_slice(const mp_table* t) {
   if (!t) return 0;
@@ -588,16 +596,10 @@ int mp_verify_shuffle_chain_dev(mp_table* t, size_t tables, uint32_t links, cons
   MP_TRY
   MP_ENTER(t->ctx);
   NoPipeline nopipe(t);
-  // one chain equation holds at most 32 767 distinct points ((L + 1) 2N decks + L (11m + 8) proof elements + key): longer chains are
-  // verified as consecutive sub-chains (the decks array is link-major, so a sub-chain is a contiguous slice)
-  const size_t per_link = (size_t)2 * t->N + 11 * t->m + 8, fixed_part = (size_t)2 * t->N + 1;
+  // chains longer than one equation takes: consecutive sub-chains (the decks array is link-major, so a sub-chain is a contiguous slice)
+  const uint32_t lmax = chain_links_max(t);
+  if (!lmax) return fail(MP_ERR_INTERNAL, "mp_verify_shuffle_chain_dev: deck too large for one chain equation");
   const size_t pb = t->point_bytes, deck_bytes = (size_t)2 * t->N * pb, psz = proof_size_bytes(t->m, t->n, (uint32_t)pb);
-  // (one link does not always fit 32 767 points -- m = 2048, n = 2: 4N + 11m + 9 = 38 921 -- but it fits one bucket job: the kernel sorts
-  // up to BUCKET_TERMS_MAX = 65 535 points per window, and 4N + 11m + 9 <= 38 921 for every table mp_table_create accepts, m n <= 4096)
-  const size_t eq_cap = fixed_part + per_link > 32767 ? (size_t)65535 : 32767;
-  if (fixed_part + per_link > eq_cap) return fail(MP_ERR_INTERNAL, "mp_verify_shuffle_chain_dev: deck too large for one chain equation");
-  uint32_t lmax = std::min<uint32_t>((uint32_t)((eq_cap - fixed_part) / per_link), 1022u);      // (links 0 .. L in 10 bits of a sorted entry: kernels_bucket.hpp)
-  if (t->chain_max_links) lmax = std::max(1u, std::min(lmax, t->chain_max_links));
   auto sub_chains = [&](size_t T, const uint8_t* decks, const uint8_t* proofs, int32_t* status, const uint8_t* keys) {
     for (uint32_t j0 = 0; j0 < links; j0 += lmax) {
       const uint32_t lc = std::min(lmax, links - j0);

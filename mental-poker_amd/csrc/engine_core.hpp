@@ -955,6 +955,19 @@ struct Table : mp_table {
       }
     }
   };
+  // forks `side` off the context's stream; while it lives, kernel launches (which take their stream from the context) go to `side`
+  struct SideFork {
+    mp_ctx* c;
+    rt::Stream keep;
+    explicit SideFork(mp_ctx* ctx) : c(ctx), keep(ctx->stream) {
+      rt::event_record(c->ev_fork, keep);
+      c->stream = c->side;
+      rt::stream_wait(c->side, c->ev_fork);
+    }
+    ~SideFork() { c->stream = keep; }
+    SideFork(const SideFork&) = delete;
+    SideFork& operator=(const SideFork&) = delete;
+  };
   void prove_side_work(PlanSet& q, Workspace& w, uint32_t B, bool with_tables) {
     const ProveLay& l = q.pplan.lay;
     run_phase(q.pph[4], w, B);      // Toom-Cook (m = 2) / Karatsuba operand sums (empty when unused)
@@ -1030,14 +1043,7 @@ struct Table : mp_table {
       // deck is there) the statement hash and the scalar program behind it.  A batch that fills the chip gains nothing from
       // running them side by side; a small one hides its transcript lanes and ChaCha draws behind the group work, or the other way.
       if (overlap) {
-        struct Restore {      // (kernel launches take their stream from the context)
-          mp_ctx* c;
-          rt::Stream keep;
-          ~Restore() { c->stream = keep; }
-        } restore{ctx, s};
-        rt::event_record(ctx->ev_fork, s);
-        ctx->stream = ctx->side;
-        rt::stream_wait(ctx->side, ctx->ev_fork);
+        SideFork on_side(ctx);
         MP_RUN(k_remask, C, B, 2 * N, ra);
         run_phase(pph[0], w, B, PH_NORM, l.shuf);
         rt::event_record(ctx->ev_shuf, ctx->side);
@@ -1176,33 +1182,61 @@ struct Table : mp_table {
     for (auto& p_ : pend_pool) release(p_);
     for (auto& p_ : pend) release(p_);
   }
+  // ---- the stages the three screening passes (verify_pass, verify_group_pass, verify_chain_dev) are built from, on the context's
+  // CURRENT lane.  Wire points of batch v -> P slots, proof scalars -> S slots: input deck, shuffled deck, proof [, the proof's key];
+  // `wire`: the decks' wire words are kept for the transcript (wire_words: the small-batch plans of the per-proof passes)
+  void load_verify_inputs(Workspace& w, PlanSet& q, const VArgs& v, bool vlane, bool wire) {
+    const uint32_t B = v.B;
+    const bool keyed = v.keys != nullptr || v.kset != nullptr;
+    const VerifyLay& l = q.vplan.lay;
+    rt::dzero(w.status.p, (size_t)w.Bpad * 4, ctx->stream);
+    uint32_t* const ww = wire ? wire_words(w, B, 2) : nullptr;
+    LoadPointsArgs a{v.decks, w.P.p, w.status.p, w.Bpad, 2 * N, l.deck, ww, 0};
+    MP_RUN(k_load_points, C, B, 2 * N, a);
+    LoadPointsArgs b{v.shuf, w.P.p, w.status.p, w.Bpad, 2 * N, l.shuf, ww, wire ? 2 * N : 0};
+    MP_RUN(k_load_points, C, B, 2 * N, b);
+    ProofIoArgs pa{const_cast<uint8_t*>(v.proofs), w.S.p, w.P.p, w.status.p, q.vwire.p, w.Bpad, (uint32_t)proof_size_bytes(m, n, G_::PB)};
+    MP_RUN(k_load_proof, C, B, (uint32_t)q.vplan.wire.size(), pa);
+    if (keyed) {
+      LoadPointsArgs ka{v.kset ? gather_keys(B, v.kset, v.kidx, w.status.p, vlane) : v.keys, w.P.p, w.status.p, w.Bpad, 1, l.pk};
+      MP_RUN(k_load_points, C, B, 1, ka);
+    }
+    // decks and proof points are the P slots [0, pk); the key follows
+    check_verify_inputs(w, B, l, keyed);
+  }
+  // the transcripts of the batch: challenges and (merge) the weights of the merged equation
+  void run_transcripts(Workspace& w, PlanSet& q, uint32_t B, bool keyed, bool merged, bool wire) {
+    const VerifyLay& l = q.vplan.lay;
+    VerifyFsArgs a{};
+    a.st = statement_args(w, l.deck, l.shuf, l.cA, l.x, keyed ? l.pk : NO_SLOT);
+    if (wire) {
+      a.st.W = wire_words(w, B, 2);
+      a.st.w_deck = 0;
+      a.st.w_shuf = 2 * N;
+    }
+    a.l = l;
+    a.merge = merged ? 1u : 0u;
+    run_verify_fs(a, B);
+  }
+  // the scalars of every proof's equations [, merged into those of its one equation]
+  void run_verify_scalars(Workspace& w, PlanSet& q, uint32_t B, bool merged) {
+    VerifyScalArgs sa{w.S.p, w.P.p, w.direct.p, q.vplan.lay, q.vplan.cm, w.Bpad};
+    MP_RUN(k_verify_scal, C, B, n + 2, sa);
+    if (merged) {
+      VerifyMergeArgs ma{w.S.p, q.mjobs.p, q.mpairs.p, w.Bpad};
+      MP_RUN(k_verify_merge, C, B, (uint32_t)q.vplan.mjobs.size(), ma);
+    }
+  }
   // one pass over a batch on the context's CURRENT lane: merged = the screening equation, else equation by equation
   void verify_pass(Workspace& w, const VArgs& v, bool merged, bool vlane, uint32_t* host_flag = nullptr) {
     const uint32_t B = v.B;
     const bool keyed = v.keys != nullptr || v.kset != nullptr;
-    const uint8_t* keys = v.keys;
     PlanSet& q = pick(B, keyed);
     cur_table_group = q.table_group;
     cur_norm_chunk = q.norm_chunk;
     const VerifyLay& l = q.vplan.lay;
     rt::Stream s = ctx->stream;
-    rt::dzero(w.status.p, (size_t)w.Bpad * 4, s);
-    {
-      uint32_t* const ww = wire_words(w, B, 2);
-      LoadPointsArgs a{v.decks, w.P.p, w.status.p, w.Bpad, 2 * N, l.deck, ww, 0};
-      MP_RUN(k_load_points, C, B, 2 * N, a);
-      LoadPointsArgs b{v.shuf, w.P.p, w.status.p, w.Bpad, 2 * N, l.shuf, ww, 2 * N};
-      MP_RUN(k_load_points, C, B, 2 * N, b);
-      ProofIoArgs pa{const_cast<uint8_t*>(v.proofs), w.S.p, w.P.p, w.status.p, q.vwire.p, w.Bpad, (uint32_t)proof_size_bytes(m, n, G_::PB)};
-      MP_RUN(k_load_proof, C, B, (uint32_t)q.vplan.wire.size(), pa);
-      if (v.kset) keys = gather_keys(B, v.kset, v.kidx, w.status.p, vlane);
-      if (keyed) {
-        LoadPointsArgs ka{keys, w.P.p, w.status.p, w.Bpad, 1, l.pk};
-        MP_RUN(k_load_points, C, B, 1, ka);
-      }
-      // decks and proof points are the P slots [0, pk); the key follows
-      check_verify_inputs(w, B, l, keyed);
-    }
+    load_verify_inputs(w, q, v, vlane, true);
     // The window tables of the verifier's bases need the loaded points and nothing else: batches that do not fill the chip build
     // them on `side` while the main stream hashes the transcript and derives the scalars (the table kernel leans on HBM, the
     // transcript lanes on latency: they do not compete)
@@ -1210,33 +1244,12 @@ struct Table : mp_table {
     const bool vtab_forked = overlap_max && B <= overlap_max && ph.n_tables != 0;
     SideGuard vguard{ctx, !vtab_forked};
     if (vtab_forked) {
-      struct Restore {
-        mp_ctx* c;
-        rt::Stream keep;
-        ~Restore() { c->stream = keep; }
-      } restore{ctx, s};
-      rt::event_record(ctx->ev_fork, s);
-      ctx->stream = ctx->side;
-      rt::stream_wait(ctx->side, ctx->ev_fork);
+      SideFork on_side(ctx);
       run_tables(ph, w, B, w.NS.p);
       rt::event_record(ctx->ev_tab, ctx->side);
     }
-    {
-      VerifyFsArgs a{};
-      a.st = statement_args(w, l.deck, l.shuf, l.cA, l.x, keyed ? l.pk : NO_SLOT);
-      a.st.W = wire_words(w, B, 2);
-      a.st.w_deck = 0;
-      a.st.w_shuf = 2 * N;
-      a.l = l;
-      a.merge = merged ? 1u : 0u;
-      run_verify_fs(a, B);
-      VerifyScalArgs sa{w.S.p, w.P.p, w.direct.p, l, q.vplan.cm, w.Bpad};
-      MP_RUN(k_verify_scal, C, B, n + 2, sa);
-    }
-    if (merged) {
-      VerifyMergeArgs ma{w.S.p, q.mjobs.p, q.mpairs.p, w.Bpad};
-      MP_RUN(k_verify_merge, C, B, (uint32_t)q.vplan.mjobs.size(), ma);
-    }
+    run_transcripts(w, q, B, keyed, merged, true);
+    run_verify_scalars(w, q, B, merged);
     if (vtab_forked) {
       rt::stream_wait(s, ctx->ev_tab);
       vguard.joined = true;
@@ -1321,6 +1334,21 @@ struct Table : mp_table {
         for (uint32_t j = 0; j < L; ++j) idx.push_back(j * T + t);
     std::sort(idx.begin(), idx.end());
   }
+  // what a screen of T equations of L proofs each could not clear: the members of the failing equations through the finer passes
+  // (verify_subset: level, l1, own_arenas, depth), nobody else.  `bad`: one verdict word per equation -- device words, or (mapped) the
+  // page-locked words a pipelined screen wrote, valid already.  note: the group sizes adapt to what this screen saw.  Returns the suspects
+  std::vector<uint32_t> refine_groups(const VArgs& v, const uint32_t* bad, bool mapped, uint32_t T, uint32_t L, bool vlane, bool note,
+                                      int level, uint32_t l1, bool own_arenas = true, uint32_t depth = 0) {
+    std::vector<uint32_t> words, idx;
+    if (!mapped) {
+      read_words(bad, T, words);
+      bad = words.data();
+    }
+    group_members(bad, T, L, idx);
+    if (note) note_group_verdicts(T, (uint32_t)(idx.size() / L), L);
+    verify_subset(v, idx, level, vlane, l1, own_arenas, depth);
+    return idx;
+  }
   // the proofs idx[] of batch v (ascending) through the finer passes; their status words replace the screen's marks
   // own_arenas: the caller's arenas (ws) are laid out for batch v (verify_dev); a chain call's are not (its lean workspace is cws)
   // depth: how many sub-batches lie above this one (each has gather buffers of its own: sub[lane][depth])
@@ -1393,14 +1421,10 @@ struct Table : mp_table {
       gb.alloc(T2, s, false);
       verify_group_pass(sv, L2, vlane, nullptr, gb.p);
       if (read_flag(vlane)) {
-        std::vector<uint32_t> bad, idx2;
-        read_words(gb.p, T2, bad);
-        group_members(bad.data(), T2, L2, idx2);
         // (the members of the failing sub-groups: through sub-groups an eighth the size once more if there are enough of them -- 1 024 ->
         // 128 -> 16 --, else equation by equation)
-        verify_subset(sv, idx2, L2 >= 64 ? 0 : 1, vlane, L2, true, depth + 1);
-        for (uint32_t i2 : idx2)                          // (mp_reverified_count counts proofs, not the copies that fill the last sub-group)
-          if (i2 >= distinct) n_reverified -= 1;
+        for (uint32_t i2 : refine_groups(sv, gb.p, false, T2, L2, vlane, false, L2 >= 64 ? 0 : 1, L2, true, depth + 1))
+          if (i2 >= distinct) n_reverified -= 1;          // (mp_reverified_count counts proofs, not the copies that fill the last sub-group)
       }
     } else {
       per_equation(sv);
@@ -1473,11 +1497,7 @@ struct Table : mp_table {
         note_group_verdicts(T, 0, gl);
         return;
       }
-      std::vector<uint32_t> bad, idx;
-      read_words(gbad[0].p, T, bad);
-      group_members(bad.data(), T, gl, idx);
-      note_group_verdicts(T, (uint32_t)(idx.size() / gl), gl);
-      verify_subset(v, idx, 0, false, gl);  // the members of the failing groups, nobody else
+      refine_groups(v, gbad[0].p, false, T, gl, false, true, 0, gl);
       return;
     }
     reserve_for(v.B, keyed);
@@ -1502,10 +1522,7 @@ struct Table : mp_table {
       }
       LaneSwap lane(ctx);
       if (pn.gl) {
-        std::vector<uint32_t> idx;
-        group_members(pn.h_gbad, pn.v.B / pn.gl, pn.gl, idx);
-        note_group_verdicts(pn.v.B / pn.gl, (uint32_t)(idx.size() / pn.gl), pn.gl);
-        verify_subset(pn.v, idx, 0, true, pn.gl);
+        refine_groups(pn.v, pn.h_gbad, true, pn.v.B / pn.gl, pn.gl, true, true, 0, pn.gl);
       } else {
         refine_marked(pn.v, true);          // the proofs the screen marked: the first failing check of each
       }
@@ -1566,6 +1583,18 @@ struct Table : mp_table {
   // chain plan with "links" j G + g and a chain's consecutive links G apart; kernels and lane formula are unchanged.  A failing
   // equation sends ITS G x L links through the per-link verifier.  G = the divisor of T that brings the equation nearest to the
   // group equation's size (mp_set_group_verify), with enough equations left to keep the persistent waves busy; 1 = a table on its own.
+  // members per equation: the divisor of `total` nearest to `want` (between half and twice it) whose equation -- `per` points a member
+  // and the n + 5 fixed bases -- fits one bucket job (65 535 points) and passes `fits`; 0 = there is none
+  template <class Fits>
+  uint32_t nearest_divisor(uint32_t total, uint32_t want, uint32_t per, Fits fits) const {
+    for (uint32_t d = 0; d <= want; ++d)
+      for (int sgn = 1; sgn >= -1; sgn -= 2) {
+        const int64_t L = (int64_t)want + sgn * (int64_t)d;
+        if (L < 2 || 2 * L < (int64_t)want || L > 2 * (int64_t)want || (uint64_t)L * per + n + 5 > BUCKET_TERMS_MAX || !fits((uint32_t)L)) continue;
+        if (total % (uint32_t)L == 0) return (uint32_t)L;
+      }
+    return 0;
+  }
   uint32_t chain_points_per_table(uint32_t L, bool keyed) const { return (L + 1) * 2 * N + L * (11 * m + 8) + (keyed ? 1u : 0u); }
   uint32_t chain_group_of(uint32_t T, uint32_t L, bool keyed) const {
     // (an explicit mp_set_chain_group is honoured whatever mp_set_group_verify says; the automatic rule follows the group equations')
@@ -1581,63 +1610,68 @@ struct Table : mp_table {
       if (group_points_wg && (uint64_t)want_wg * per >= GROUP_WG_POINTS_MIN) want = std::max(want, want_wg);
     }
     if (want < 2) return 1;
-    for (uint32_t d = 0; d <= want; ++d)
-      for (int sgn = 1; sgn >= -1; sgn -= 2) {
-        const int64_t G = (int64_t)want + sgn * (int64_t)d;
-        // (12 bits of link in a term's tile source: k_chain_tile)
-        if (G < 2 || 2 * G < (int64_t)want || G > 2 * (int64_t)want || (uint64_t)G * per + n + 5 > BUCKET_TERMS_MAX || (uint64_t)G * (L + 1) > 4094) continue;
-        if (T % (uint32_t)G == 0) return (uint32_t)G;
+    // (12 bits of link in a term's tile source: k_chain_tile)
+    const uint32_t G = nearest_divisor(T, want, per, [&](uint32_t g) { return (uint64_t)g * (L + 1) <= 4094; });
+    return G ? G : 1;
+  }
+  // The plan of an equation over `links` lanes: ONE bucket MSM over K distinct points + the fixed-base part.  `terms(var)` enumerates the
+  // K variable terms -- var(term, point): where chains and groups differ --; shared: the window width from K, the fixed bases (the scalar of
+  // one is a sum over the equation's links, one lane adding them up in k_chain_scalars: in runs of at most 64 -- a base then appears
+  // ceil(links / 64) times in the fixed-base part -- so that no lane of that kernel runs 1 024 products in a row), counts and uploads
+  template <class Terms>
+  void build_equation_plan(ChainPlan& p, const VerifyLay& l, uint32_t L, uint32_t G, bool keyed, uint32_t K, uint32_t links, Terms terms) {
+    p.ph = Phase();
+    p.cterms.clear();
+    p.tile_src.clear();
+    p.L = L;
+    p.G = G;
+    p.keyed = keyed;
+    uint32_t next_partial = 1;                  // J slot 0 = the equation's value
+    const uint32_t bits = bucket_bits_of(K);
+    PhaseBuilder pb(p.ph, next_partial, FCHUNK, VCHUNK, 1u, bk_windows(R::BITS, bits), 1u, bits);
+    pb.begin(0);
+    terms([&](ChainTerm ct, uint32_t point) {
+      pb.var((uint32_t)p.cterms.size(), point);
+      p.cterms.push_back(ct);
+    });
+    p.K = (uint32_t)p.cterms.size();
+    FixedBases fb{n};
+    for (uint32_t f = 0; f < fb.count(); ++f) {
+      if (keyed && f == fb.pk()) continue;
+      for (uint32_t j0 = 0; j0 < links; j0 += 64u) {
+        pb.fixed((uint32_t)p.cterms.size(), f);
+        p.cterms.push_back(ChainTerm{l.mfix + f, j0, std::min(64u, links - j0), NO_SLOT, 1});
       }
-    return 1;
+    }
+    p.nfix = (uint32_t)p.cterms.size() - p.K;
+    pb.end();
+    p.nJ = next_partial;
+    p.dev.upload(p.ph, ctx->stream);
+    p.dterms.upload(p.cterms, ctx->stream);
   }
   void build_chain_plan(uint32_t L, bool keyed, uint32_t G = 1) {
     if (chain.L == L && chain.keyed == keyed && chain.G == G) return;
     if (keyed) ensure_keyed();
-    PlanSet& q = (keyed ? psk : ps)[0];
-    const VerifyLay& l = q.vplan.lay;
-    chain.ph = Phase();
-    chain.cterms.clear();
-    chain.tile_src.clear();
-    chain.L = L;
-    chain.G = G;
-    chain.keyed = keyed;
-    uint32_t next_partial = 1;                  // J slot 0 = the chain equation's value
-    const uint32_t cbits = bucket_bits_of(G * ((L + 1) * 2 * N + L * (l.pk - l.cA) + (keyed ? 1u : 0u)));
-    PhaseBuilder pb(chain.ph, next_partial, FCHUNK, VCHUNK, 1u, bk_windows(R::BITS, cbits), 1u, cbits);
-    pb.begin(0);
-    // (a term's point: its index in the equation's contiguous run -- k_chain_tile copies it there from slot | link << 20)
-    auto var = [&](ChainTerm ct, uint32_t pslot, uint32_t link) {
-      pb.var((uint32_t)chain.cterms.size(), (uint32_t)chain.cterms.size());
-      chain.tile_src.push_back(pslot | (link << 20));
-      chain.cterms.push_back(ct);
-    };
-    // ("link" j G + g of the equation = link j of member g)
-    for (uint32_t g = 0; g < G; ++g)
-      for (uint32_t j = 0; j <= L; ++j)
-        for (uint32_t i = 0; i < 2 * N; ++i) {
-          if (j == 0) var(ChainTerm{l.mvar + l.deck + i, g, 1, NO_SLOT, G}, l.deck + i, g);
-          else if (j < L) var(ChainTerm{l.mvar + l.deck + i, j * G + g, 1, l.mvar + l.shuf + i, G}, l.deck + i, j * G + g);
-          else var(ChainTerm{l.mvar + l.shuf + i, (L - 1) * G + g, 1, NO_SLOT, G}, l.shuf + i, (L - 1) * G + g);
-        }
-    for (uint32_t j = 0; j < L * G; ++j)
-      for (uint32_t slot = l.cA; slot < l.pk; ++slot) var(ChainTerm{l.mvar + slot, j, 1, NO_SLOT, 1}, slot, j);
-    if (keyed)
-      for (uint32_t g = 0; g < G; ++g) var(ChainTerm{l.mvar + l.pk, g, L, NO_SLOT, G}, l.pk, g);      // one key term per member
-    chain.K = (uint32_t)chain.cterms.size();
-    // (the scalar of a fixed base: a sum over the equation's L G links, in runs of at most 64 -- as in the group plan below)
-    FixedBases fb{n};
-    for (uint32_t f = 0; f < fb.count(); ++f) {
-      if (keyed && f == fb.pk()) continue;
-      for (uint32_t j0 = 0; j0 < L * G; j0 += 64u) {
-        pb.fixed((uint32_t)chain.cterms.size(), f);
-        chain.cterms.push_back(ChainTerm{l.mfix + f, j0, std::min(64u, L * G - j0), NO_SLOT, 1});
-      }
-    }
-    chain.nfix = (uint32_t)chain.cterms.size() - chain.K;
-    pb.end();
-    chain.nJ = next_partial;
-    chain.dev.upload(chain.ph, ctx->stream);
-    chain.dterms.upload(chain.cterms, ctx->stream);
+    const VerifyLay& l = (keyed ? psk : ps)[0].vplan.lay;
+    build_equation_plan(chain, l, L, G, keyed, G * ((L + 1) * 2 * N + L * (l.pk - l.cA) + (keyed ? 1u : 0u)), L * G, [&](auto term) {
+      // (a term's point: its index in the equation's contiguous run -- k_chain_tile copies it there from slot | link << 20)
+      auto var = [&](ChainTerm ct, uint32_t pslot, uint32_t link) {
+        chain.tile_src.push_back(pslot | (link << 20));
+        term(ct, (uint32_t)chain.cterms.size());
+      };
+      // ("link" j G + g of the equation = link j of member g)
+      for (uint32_t g = 0; g < G; ++g)
+        for (uint32_t j = 0; j <= L; ++j)
+          for (uint32_t i = 0; i < 2 * N; ++i) {
+            if (j == 0) var(ChainTerm{l.mvar + l.deck + i, g, 1, NO_SLOT, G}, l.deck + i, g);
+            else if (j < L) var(ChainTerm{l.mvar + l.deck + i, j * G + g, 1, l.mvar + l.shuf + i, G}, l.deck + i, j * G + g);
+            else var(ChainTerm{l.mvar + l.shuf + i, (L - 1) * G + g, 1, NO_SLOT, G}, l.shuf + i, (L - 1) * G + g);
+          }
+      for (uint32_t j = 0; j < L * G; ++j)
+        for (uint32_t slot = l.cA; slot < l.pk; ++slot) var(ChainTerm{l.mvar + slot, j, 1, NO_SLOT, 1}, slot, j);
+      if (keyed)
+        for (uint32_t g = 0; g < G; ++g) var(ChainTerm{l.mvar + l.pk, g, L, NO_SLOT, G}, l.pk, g);      // one key term per member
+    });
     chain.dtile_src.upload(chain.tile_src, ctx->stream);
   }
   size_t chain_lane_bytes(uint32_t, bool keyed) override {
@@ -1651,80 +1685,87 @@ struct Table : mp_table {
   }
   size_t chain_lanes_held() const override { return cws.cap; }
   uint32_t chain_group_size(size_t T, uint32_t L, bool keyed) const override { return T < 0x7FFFFFFFu ? chain_group_of((uint32_t)T, L, keyed) : 1u; }
+  // ---- the equation stages of a chain / group pass: T equations of L links each over plan p, lane of (link j, equation t) = j T + t.
+  // Room for the weights, the scalars of the terms and their bucket digits (before the weights are drawn)
+  void size_equations(const ChainPlan& p, uint32_t T, uint32_t L) {
+    const uint32_t Tpad = (T + 63u) & ~63u;
+    chain_cw.alloc((size_t)L * Tpad * 8, ctx->stream, false);
+    chain_cs.alloc((size_t)(p.K + p.nfix) * Tpad * 8, ctx->stream);
+    chain_d8.alloc((size_t)p.dev.b_dig_bytes * Tpad, ctx->stream);
+  }
+  // what the equations of a chain pass and of a group pass do not share
+  struct EquationArgs {
+    uint32_t T, L;
+    bool vlane;
+    const char* too_many;      // (what run_bucket says when T is beyond one launch)
+    uint32_t pk, G;            // ChainVerdictArgs: the key's P slot (chains whose links share it), tables per equation
+    uint32_t* flag;            // raised if some equation fails (null: the lane's flag word)
+    uint32_t* gbad;            // [T] which (null: the lane's gbad[] words, sized here)
+    int32_t* status;           // the caller's status words
+  };
+  // With weights (run_chain_weights) and the proofs' merged scalars in place: one scalar per distinct point / fixed base, the points as one
+  // contiguous run per equation (tile(run): k_chain_tile / k_group_tile; tiled = false: the bucket kernel takes them from their P slots),
+  // ONE bucket MSM + fixed-base part per equation, the verdicts: flag, gbad[t], and in e.status 0 for every link of an equation that holds
+  // (final), MP_ERR_INTERNAL for those of the others until the finer passes have given each its own word
+  template <class Tile>
+  void run_equations(Workspace& w, ChainPlan& p, const EquationArgs& e, bool tiled, Tile tile) {
+    const uint32_t T = e.T, Tpad = (T + 63u) & ~63u, nterms = p.K + p.nfix;
+    rt::Stream s = ctx->stream;
+    ChainScalArgs ca{w.S.p, chain_cw.p, chain_cs.p, p.dterms.p, w.Bpad, Tpad, T};
+    MP_RUN(k_chain_scalars, C, T, nterms, ca);
+    PhaseDev& ph = p.dev;
+    const uint32_t* run = nullptr;
+    if (tiled) {
+      DevBuf<uint32_t>& gt = gtile[e.vlane ? 1 : 0];
+      gt.alloc((size_t)T * p.K * G_::PW, s, false);
+      tile(gt.p);
+      run = gt.p;
+    }
+    run_bucket(w, ph, chain_cs.p, Tpad, chain_d8.p, (size_t)ph.b_dig_bytes, T, T, e.too_many, run, p.K);
+    FixedArgs fx{chain_cs.p, w.J.p, FB.p, ph.fjobs.p, ph.fterms.p, w.Bpad, fbg, Tpad};
+    MP_RUN(k_fixed_msm, C, T, ph.n_f, fx);
+    if (ph.n_c0) {
+      CombineArgs cb0{w.J.p, w.P.p, ph.cjobs0.p, ph.cterms0.p, w.Bpad};
+      MP_RUN(k_combine, C, T, ph.n_c0, cb0);
+    }
+    CombineArgs cb{w.J.p, w.P.p, ph.cjobs.p, ph.cterms.p, w.Bpad};
+    MP_RUN(k_combine, C, T, ph.n_c, cb);
+    uint32_t* gb = e.gbad;
+    if (!gb) {
+      gbad[e.vlane ? 1 : 0].alloc(T, s, false);
+      gb = gbad[e.vlane ? 1 : 0].p;
+    }
+    ChainVerdictArgs va{w.J.p, w.direct.p, w.status.p, e.flag ? e.flag : flag_word(e.vlane, s), gb, w.Bpad, T, e.L, 0u, w.P.p, e.pk, e.G, e.status, nullptr};
+    run_chain_verdict(va);
+  }
   void verify_chain_dev(size_t T_, uint32_t L, const uint8_t* decks, const uint8_t* proofs, int32_t* status, const uint8_t* keys) override {
     const uint32_t T = (uint32_t)T_, B = T * L;
     const bool keyed = keys != nullptr;
     // G tables per equation: Tq equations of Lq "links" each, lane of (link, equation) = link Tq + equation as before
-    const uint32_t G = chain_group_of(T, L, keyed), Tq = T / G, Lq = L * G, Tpad = (Tq + 63u) & ~63u;
+    const uint32_t G = chain_group_of(T, L, keyed), Tq = T / G, Lq = L * G;
     build_chain_plan(L, keyed, G);
     PlanSet& q = (keyed ? psk : ps)[0];
     const VerifyLay& l = q.vplan.lay;
-    rt::Stream s = ctx->stream;
     Workspace& w = cws;
     w.fw = G_::FW;
-    w.ensure(B, l.nS, l.nP, std::max(chain.nJ, 8u), 0, 0, nwin, stage_words_needed(), s, 0);
-    const size_t deck_bytes = (size_t)2 * N * G_::PB;
-    rt::dzero(w.status.p, (size_t)w.Bpad * 4, s);
-    {
-      LoadPointsArgs a{decks, w.P.p, w.status.p, w.Bpad, 2 * N, l.deck};
-      MP_RUN(k_load_points, C, B, 2 * N, a);
-      LoadPointsArgs b{decks + (size_t)T * deck_bytes, w.P.p, w.status.p, w.Bpad, 2 * N, l.shuf};
-      MP_RUN(k_load_points, C, B, 2 * N, b);
-      ProofIoArgs pa{const_cast<uint8_t*>(proofs), w.S.p, w.P.p, w.status.p, q.vwire.p, w.Bpad, (uint32_t)proof_size_bytes(m, n, G_::PB)};
-      MP_RUN(k_load_proof, C, B, (uint32_t)q.vplan.wire.size(), pa);
-      if (keyed) {
-        LoadPointsArgs ka{keys, w.P.p, w.status.p, w.Bpad, 1, l.pk};
-        MP_RUN(k_load_points, C, B, 1, ka);
-      }
-      check_verify_inputs(w, B, l, keyed);
-    }
-    {
-      VerifyFsArgs a{};
-      a.st = statement_args(w, l.deck, l.shuf, l.cA, l.x, keyed ? l.pk : NO_SLOT);
-      a.l = l;
-      a.merge = 1u;
-      run_verify_fs(a, B);
-      VerifyScalArgs sa{w.S.p, w.P.p, w.direct.p, l, q.vplan.cm, w.Bpad};
-      MP_RUN(k_verify_scal, C, B, n + 2, sa);
-      VerifyMergeArgs ma{w.S.p, q.mjobs.p, q.mpairs.p, w.Bpad};
-      MP_RUN(k_verify_merge, C, B, (uint32_t)q.vplan.mjobs.size(), ma);
-    }
+    w.ensure(B, l.nS, l.nP, std::max(chain.nJ, 8u), 0, 0, nwin, stage_words_needed(), ctx->stream, 0);
+    // (link j of table t: deck row j T + t, shuffled deck row (j + 1) T + t -- the same index into the array one deck further on)
+    const VArgs cv{B, decks, decks + (size_t)T * 2 * N * G_::PB, proofs, status, keys, nullptr, nullptr};
+    load_verify_inputs(w, q, cv, false, false);
+    run_transcripts(w, q, B, keyed, true, false);
+    run_verify_scalars(w, q, B, true);
     // the chain equation: weights, one scalar per distinct point / fixed base, ONE bucket MSM + fixed-base part per table
-    const uint32_t nterms = chain.K + chain.nfix;
-    chain_cw.alloc((size_t)Lq * Tpad * 8, s, false);
-    chain_cs.alloc((size_t)nterms * Tpad * 8, s);
-    chain_d8.alloc((size_t)chain.dev.b_dig_bytes * Tpad, s);
-    run_chain_weights(w, Tpad, Tq, Lq);
-    ChainScalArgs ca{w.S.p, chain_cw.p, chain_cs.p, chain.dterms.p, w.Bpad, Tpad, Tq};
-    MP_RUN(k_chain_scalars, C, Tq, nterms, ca);
-    PhaseDev& ph = chain.dev;
-    DevBuf<uint32_t>& gt = gtile[0];
-    gt.alloc((size_t)Tq * chain.K * G_::PW, s, false);
-    ChainTileArgs ta{w.P.p, gt.p, chain.dtile_src.p, w.Bpad, Tq, chain.K};
-    if ((uint64_t)Tq * chain.K >= ((uint64_t)1 << 32)) throw std::runtime_error("chain verification: too many tables for one launch");
-    MP_RUN(k_chain_tile, C, Tq * chain.K, 1, ta);
-    run_bucket(w, ph, chain_cs.p, Tpad, chain_d8.p, (size_t)ph.b_dig_bytes, Tq, Tq, "chain verification: too many tables for one launch", gt.p, chain.K);
-    FixedArgs fx{chain_cs.p, w.J.p, FB.p, ph.fjobs.p, ph.fterms.p, w.Bpad, fbg, Tpad};
-    MP_RUN(k_fixed_msm, C, Tq, ph.n_f, fx);
-    if (ph.n_c0) {
-      CombineArgs cb0{w.J.p, w.P.p, ph.cjobs0.p, ph.cterms0.p, w.Bpad};
-      MP_RUN(k_combine, C, Tq, ph.n_c0, cb0);
-    }
-    CombineArgs cb{w.J.p, w.P.p, ph.cjobs.p, ph.cterms.p, w.Bpad};
-    MP_RUN(k_combine, C, Tq, ph.n_c, cb);
-    gbad[0].alloc(Tq, s, false);
-    // (the caller's words: 0 for every link of every table whose chain equation holds, MP_ERR_INTERNAL for the others until the per-link
-    // verifier below has looked at them)
-    ChainVerdictArgs va{w.J.p, w.direct.p, w.status.p, flag_word(false, s), gbad[0].p, w.Bpad, Tq, Lq, 0u, w.P.p, keyed ? l.pk : NO_SLOT, G, status, nullptr};
-    run_chain_verdict(va);
+    size_equations(chain, Tq, Lq);
+    run_chain_weights(w, (Tq + 63u) & ~63u, Tq, Lq);
+    const EquationArgs e{Tq, Lq, false, "chain verification: too many tables for one launch", keyed ? l.pk : NO_SLOT, G, nullptr, nullptr, status};
+    run_equations(w, chain, e, true, [&](uint32_t* run) {
+      ChainTileArgs ta{w.P.p, run, chain.dtile_src.p, w.Bpad, Tq, chain.K};
+      if ((uint64_t)Tq * chain.K >= ((uint64_t)1 << 32)) throw std::runtime_error("chain verification: too many tables for one launch");
+      MP_RUN(k_chain_tile, C, Tq * chain.K, 1, ta);
+    });
     if (!read_flag(false)) return;
-    // some equation failed: the per-link verifier gives every link of ITS tables its exact status (link j of table t: deck row j T + t,
-    // shuffled deck row (j + 1) T + t -- the same index into the array one deck further on); the other tables' verdicts stand
-    std::vector<uint32_t> bad, idx;
-    read_words(gbad[0].p, Tq, bad);
-    group_members(bad.data(), Tq, Lq, idx);
-    const VArgs cv{B, decks, decks + (size_t)T * deck_bytes, proofs, status, keys, nullptr, nullptr};
-    verify_subset(cv, idx, 0, false, 0, false);
+    // some equation failed: the per-link verifier gives every link of ITS tables its exact status; the other tables' verdicts stand
+    refine_groups(cv, gbad[0].p, false, Tq, Lq, false, false, 0, 0, false);
   }
 
   // ---------------------------------------------------------------- group verification (round 4)
@@ -1781,8 +1822,7 @@ struct Table : mp_table {
     group_points_wg = points > 65535u ? points : 0u;
     group_min_batch = (uint32_t)std::min<size_t>(min_batch, 0x7FFFFFFFu);
   }
-  // proofs per group for a batch of B: the divisor of B nearest to the wanted size (between half and twice it) whose equation
-  // fits one bucket job (65 535 points); 0 = this batch takes the per-proof screen
+  // proofs per group for a batch of B (nearest_divisor of the wanted size); 0 = this batch takes the per-proof screen
   uint32_t group_size_of(size_t B) const override { return B < 0x7FFFFFFFu ? group_size((uint32_t)B, false) : 0; }
   uint32_t group_size(uint32_t B, bool keyed) const {
     const uint32_t per = 4 * N + 11 * m + 8 + (keyed ? 1u : 0u);
@@ -1802,14 +1842,8 @@ struct Table : mp_table {
     // (under sustained rejection the groups shrink: note_group_verdicts below)
     if (want >= 4) want = std::max<uint32_t>(want >> adapt_shift, 4u);
     if (want < 2) return 0;
-    for (uint32_t d = 0; d <= want; ++d)
-      for (int sgn = 1; sgn >= -1; sgn -= 2) {
-        const int64_t L = (int64_t)want + sgn * (int64_t)d;
-        // (without the contiguous run of k_group_tile a sorted entry names member and slot: 10 bits of link -- kernels_bucket.hpp)
-        if (L < 2 || 2 * L < (int64_t)want || L > 2 * (int64_t)want || (uint64_t)L * per + n + 5 > BUCKET_TERMS_MAX || (!bk_tile && L > 1023)) continue;
-        if (B % (uint32_t)L == 0) return (uint32_t)L;
-      }
-    return 0;
+    // (without the contiguous run of k_group_tile a sorted entry names member and slot: 10 bits of link -- kernels_bucket.hpp)
+    return nearest_divisor(B, want, per, [](uint32_t L) { return bk_tile || L <= 1023; });
   }
   // Groups that adapt to the rejection rate (round 5).  A group of L proofs fails if ANY member does: with a fraction p of bad proofs
   // spread over the batch, 1 - (1 - p)^L of the groups fail -- 72 % of the groups of 128 at p = 1 % -- and every member of a failing group
@@ -1850,48 +1884,22 @@ struct Table : mp_table {
     }
     std::unique_ptr<ChainPlan>& fresh = gplans[key];
     fresh.reset(new ChainPlan());
-    ChainPlan& gplan = *fresh;
     if (keyed) ensure_keyed();
-    PlanSet& q = (keyed ? psk : ps)[0];
-    const VerifyLay& l = q.vplan.lay;
-    gplan.ph = Phase();
-    gplan.cterms.clear();
-    gplan.L = L;
-    gplan.keyed = keyed;
-    uint32_t next_partial = 1;                  // J slot 0 = the group equation's value
-    const uint32_t gbits = bucket_bits_of(L * (l.pk + (keyed ? 1u : 0u)));
-    PhaseBuilder pb(gplan.ph, next_partial, FCHUNK, VCHUNK, 1u, bk_windows(R::BITS, gbits), 1u, gbits);
-    pb.begin(0);
-    for (uint32_t j = 0; j < L; ++j)
-      for (uint32_t slot = 0; slot < l.pk + (keyed ? 1u : 0u); ++slot) {      // decks, proof points [, the proof's own key]
-        // (a term's point: its index in the group's contiguous run, or the P slot | member whose lane holds it)
-        pb.var((uint32_t)gplan.cterms.size(), bk_tile ? (uint32_t)gplan.cterms.size() : (slot | (j << 20)));
-        gplan.cterms.push_back(ChainTerm{l.mvar + slot, j, 1, NO_SLOT, 1});
-      }
-    gplan.K = (uint32_t)gplan.cterms.size();
-    // (the scalar of a fixed base is a sum over the members, one lane adding them up in k_chain_scalars: in runs of at most 64 members --
-    // a base then appears ceil(L / 64) times in the fixed-base part -- so that no lane of that kernel runs 1 024 products in a row)
-    FixedBases fb{n};
-    for (uint32_t f = 0; f < fb.count(); ++f) {
-      if (keyed && f == fb.pk()) continue;
-      for (uint32_t j0 = 0; j0 < L; j0 += 64u) {
-        pb.fixed((uint32_t)gplan.cterms.size(), f);
-        gplan.cterms.push_back(ChainTerm{l.mfix + f, j0, std::min(64u, L - j0), NO_SLOT, 1});
-      }
-    }
-    gplan.nfix = (uint32_t)gplan.cterms.size() - gplan.K;
-    pb.end();
-    gplan.nJ = next_partial;
-    gplan.dev.upload(gplan.ph, ctx->stream);
-    gplan.dterms.upload(gplan.cterms, ctx->stream);
-    return gplan;
+    const VerifyLay& l = (keyed ? psk : ps)[0].vplan.lay;
+    const uint32_t per = l.pk + (keyed ? 1u : 0u);      // decks, proof points [, the proof's own key]
+    build_equation_plan(*fresh, l, L, 1, keyed, L * per, L, [&](auto term) {
+      for (uint32_t j = 0; j < L; ++j)
+        for (uint32_t slot = 0; slot < per; ++slot)
+          // (a term's point: its index in the group's contiguous run, or the P slot | member whose lane holds it)
+          term(ChainTerm{l.mvar + slot, j, 1, NO_SLOT, 1}, bk_tile ? j * per + slot : (slot | (j << 20)));
+    });
+    return *fresh;
   }
   // the group pass on the context's CURRENT lane; the flag word (host_flag, or vflag) is raised if some group needs a closer look
-  // and gbad[t] says which (null: nobody asks)
+  // and gbad_out[t] says which
   void verify_group_pass(const VArgs& v, uint32_t L, bool vlane, uint32_t* host_flag, uint32_t* gbad_out) {
-    const uint32_t B = v.B, T = B / L, Tpad = (T + 63u) & ~63u;
+    const uint32_t B = v.B, T = B / L;
     const bool keyed = v.keys != nullptr || v.kset != nullptr;
-    const uint8_t* keys = v.keys;
     ChainPlan& gplan = build_group_plan(L, keyed);
     PlanSet& q = (keyed ? psk : ps)[0];
     const VerifyLay& l = q.vplan.lay;
@@ -1901,82 +1909,28 @@ struct Table : mp_table {
     Workspace& w = vlane ? gws : ws;
     w.fw = G_::FW;
     w.ensure(B, l.nS, l.nP, std::max(gplan.nJ, 8u), 0, 0, nwin, stage_words_needed(), s, 0);
-    rt::dzero(w.status.p, (size_t)w.Bpad * 4, s);
-    {
-      LoadPointsArgs a{v.decks, w.P.p, w.status.p, w.Bpad, 2 * N, l.deck};
-      MP_RUN(k_load_points, C, B, 2 * N, a);
-      LoadPointsArgs b{v.shuf, w.P.p, w.status.p, w.Bpad, 2 * N, l.shuf};
-      MP_RUN(k_load_points, C, B, 2 * N, b);
-      ProofIoArgs pa{const_cast<uint8_t*>(v.proofs), w.S.p, w.P.p, w.status.p, q.vwire.p, w.Bpad, (uint32_t)proof_size_bytes(m, n, G_::PB)};
-      MP_RUN(k_load_proof, C, B, (uint32_t)q.vplan.wire.size(), pa);
-      if (v.kset) keys = gather_keys(B, v.kset, v.kidx, w.status.p, vlane);
-      if (keyed) {
-        LoadPointsArgs ka{keys, w.P.p, w.status.p, w.Bpad, 1, l.pk};
-        MP_RUN(k_load_points, C, B, 1, ka);
-      }
-      check_verify_inputs(w, B, l, keyed);
-    }
-    {
-      VerifyFsArgs a{};
-      a.st = statement_args(w, l.deck, l.shuf, l.cA, l.x, keyed ? l.pk : NO_SLOT);
-      a.l = l;
-      a.merge = 1u;
-      run_verify_fs(a, B);
-    }
-    const uint32_t nterms = gplan.K + gplan.nfix;
-    chain_cw.alloc((size_t)L * Tpad * 8, s, false);
-    chain_cs.alloc((size_t)nterms * Tpad * 8, s);
-    chain_d8.alloc((size_t)gplan.dev.b_dig_bytes * Tpad, s);
+    load_verify_inputs(w, q, v, vlane, false);
+    run_transcripts(w, q, B, keyed, true, false);
+    size_equations(gplan, T, L);
     {
       // the group weights need the transcripts' final states and nothing else, and one lane per GROUP hashes them (2 048 lanes, 64
       // BLAKE2s blocks in a row: 2.5 ms of latency at 262 144 proofs): on `side`, beside the coefficient programs of the proofs
       SideGuard wguard{ctx, false};
-      rt::event_record(ctx->ev_fork, s);
-      rt::stream_wait(ctx->side, ctx->ev_fork);
       {
-        struct Restore {
-          mp_ctx* c;
-          rt::Stream keep;
-          ~Restore() { c->stream = keep; }
-        } restore{ctx, s};
-        ctx->stream = ctx->side;
-        run_chain_weights(w, Tpad, T, L);
+        SideFork on_side(ctx);
+        run_chain_weights(w, (T + 63u) & ~63u, T, L);
         rt::event_record(ctx->ev_tab, ctx->side);
       }
-      VerifyScalArgs sa{w.S.p, w.P.p, w.direct.p, l, q.vplan.cm, w.Bpad};
-      MP_RUN(k_verify_scal, C, B, n + 2, sa);
-      VerifyMergeArgs ma{w.S.p, q.mjobs.p, q.mpairs.p, w.Bpad};
-      MP_RUN(k_verify_merge, C, B, (uint32_t)q.vplan.mjobs.size(), ma);
+      run_verify_scalars(w, q, B, true);
       rt::stream_wait(s, ctx->ev_tab);
       wguard.joined = true;
     }
-    ChainScalArgs ca{w.S.p, chain_cw.p, chain_cs.p, gplan.dterms.p, w.Bpad, Tpad, T};
-    MP_RUN(k_chain_scalars, C, T, nterms, ca);
-    PhaseDev& ph = gplan.dev;
-    const uint32_t* tile = nullptr;
-    if (bk_tile) {
-      const uint32_t per = l.pk + (keyed ? 1u : 0u);
-      DevBuf<uint32_t>& gt = gtile[vlane ? 1 : 0];
-      gt.alloc((size_t)T * gplan.K * G_::PW, s, false);
-      GroupTileArgs ta{w.P.p, gt.p, w.Bpad, T, per, gplan.K};
+    const uint32_t per = l.pk + (keyed ? 1u : 0u);
+    const EquationArgs e{T, L, vlane, "group verification: too many groups for one launch", NO_SLOT, 1u, host_flag, gbad_out, v.status};
+    run_equations(w, gplan, e, bk_tile, [&](uint32_t* run) {
+      GroupTileArgs ta{w.P.p, run, w.Bpad, T, per, gplan.K};
       MP_RUN(k_group_tile, C, B, per, ta);
-      tile = gt.p;
-    }
-    run_bucket(w, ph, chain_cs.p, Tpad, chain_d8.p, (size_t)ph.b_dig_bytes, T, T, "group verification: too many groups for one launch", tile, gplan.K);
-    FixedArgs fx{chain_cs.p, w.J.p, FB.p, ph.fjobs.p, ph.fterms.p, w.Bpad, fbg, Tpad};
-    MP_RUN(k_fixed_msm, C, T, ph.n_f, fx);
-    if (ph.n_c0) {
-      CombineArgs cb0{w.J.p, w.P.p, ph.cjobs0.p, ph.cterms0.p, w.Bpad};
-      MP_RUN(k_combine, C, T, ph.n_c0, cb0);
-    }
-    CombineArgs cb{w.J.p, w.P.p, ph.cjobs.p, ph.cterms.p, w.Bpad};
-    MP_RUN(k_combine, C, T, ph.n_c, cb);
-    uint32_t* fl = host_flag;
-    if (!fl) fl = flag_word(vlane, s);
-    // (the caller's words: zeros for the members of the groups whose equation holds -- final --, MP_ERR_INTERNAL for those of the others
-    // until the finer passes have given each its own word)
-    ChainVerdictArgs va{w.J.p, w.direct.p, w.status.p, fl, gbad_out, w.Bpad, T, L, 0u, w.P.p, NO_SLOT, 1u, v.status, nullptr};
-    run_chain_verdict(va);
+    });
   }
 
   // ---------------------------------------------------------------- building blocks (ad-hoc plans)
