@@ -46,7 +46,8 @@ SOURCES = ["capi.hip"] + [f % c for c in ("stark", "bn254", "secp256k1", "bls12_
 
 def build(verbose=False):
     """compile the HIP engine for gfx950 in-tree -> mental-poker_amd/libmpshuffle.so
-    (one translation unit per curve, compiled in parallel, objects cached under csrc/_obj)"""
+    (one translation unit per curve, compiled in parallel, objects cached under csrc/_obj), and beside it the test tools
+    tools/quadcheck/quad_check and tools/primcheck/libprimcheck.so"""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(HERE, "csrc")
     objdir = os.path.join(csrc, "_obj")
@@ -86,13 +87,45 @@ def build(verbose=False):
         except (subprocess.CalledProcessError, OSError) as e:
             print("warning: tools/quadcheck/quad_check did not build (%s); the library is unaffected" % e, flush=True)
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + 1) as ex:
+    probe_dir = os.path.join(ROOT, "tools", "primcheck")
+    probe_src = os.path.join(probe_dir, "prim_check.hip")
+    probe_lib = os.path.join(probe_dir, "libprimcheck.so")
+
+    def compile_probe(curve_id):
+        """tools/primcheck/prim_check.hip: one field / group operation per lane, for tests/test_gpu_primitives.py.  One object per curve,
+        with EXACTLY the library's flags (the code generation under test is the library's); a shared object of its own, nothing of it
+        goes into libmpshuffle.so"""
+        os.makedirs(os.path.join(probe_dir, "_obj"), exist_ok=True)
+        obj = os.path.join(probe_dir, "_obj", "prim_check_%d.o" % curve_id)
+        if os.path.exists(obj) and os.path.getmtime(obj) >= max(hdr_time, os.path.getmtime(probe_src)):
+            return obj, False
+        cmd = [hipcc] + flags + ["-DPRIM_CURVE=%d" % curve_id, "-I", csrc, "-c", probe_src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        return obj, True
+
+    # The library's translation units are queued first and the library is linked as soon as THEY are done; the probe's objects
+    # share the pool and are collected afterwards, so the library never waits for the probe's link (they do compete for cores).
+    ex = ThreadPoolExecutor(max_workers=len(SOURCES) + 1 + len(CURVE_IDS))
+    try:
+        res_f = [ex.submit(compile_one, s) for s in SOURCES]
         chk = ex.submit(compile_check)
-        res = list(ex.map(compile_one, SOURCES))
+        probe_f = [ex.submit(compile_probe, k) for k in sorted(CURVE_IDS.values())] if os.path.exists(probe_src) else []
+        res = [f.result() for f in res_f]
+        objs = [r[0] for r in res]
+        if any(r[1] for r in res) or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(o) for o in objs):
+            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", LIB_PATH] + objs      # serialize_host.hpp uses std::thread
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.check_call(cmd)
         chk.result()
-    objs = [r[0] for r in res]
-    if any(r[1] for r in res) or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(o) for o in objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", LIB_PATH] + objs      # serialize_host.hpp uses std::thread
+        probe = [f.result() for f in probe_f]      # (a probe that does not compile fails the build: its tests do not skip)
+    finally:
+        ex.shutdown(wait=True)
+    if probe and (any(r[1] for r in probe) or not os.path.exists(probe_lib)
+                  or os.path.getmtime(probe_lib) < max(os.path.getmtime(r[0]) for r in probe)):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", probe_lib] + [r[0] for r in probe]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

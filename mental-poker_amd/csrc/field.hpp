@@ -11,9 +11,14 @@
 //      `acc = a*b + acc` multiply-adds with NO carry handling; additions / subtractions fold a weak reduction into their single signed
 //      carry pass.  Three flavours of the modulus: sparse (STARK 2^251 + 17*2^192 + 1: 2 reduction multiplies per column), signed
 //      sparse (secp256k1 2^256 - 2^32 - 977, `PM29`), dense (bn254, BLS12-377, `DENSE29`: full Montgomery reduction, quotient estimate
-//      by one multiply).  Plain C, identical on host and device.  All base fields use it: every VALU instruction costs a 4-cycle issue
-//      slot on gfx950 whatever it is, so the form with the fewest instructions wins, and (1) pays one v_addc per mad.
-//      Checked against a schoolbook big-integer reference: tests/cpp/field_check.cpp.
+//      by one multiply).  Plain C; host and device share the algorithm but not every instruction: under __HIP_DEVICE_COMPILE__ the
+//      multiply-add chains are pinned with empty asm statements (MP_CHAIN, MP_OPAQUE) and mont_sub_step multiplies by a negated
+//      constant held in a scalar register, where the host form subtracts a plain product.  (Form (1) differs in the algorithm itself:
+//      the device runs the product scanning of mul32 over fe_mac96, the host mul32_cios.)  All base fields use it: every VALU
+//      instruction costs a 4-cycle issue slot on gfx950 whatever it is, so the form with the fewest instructions
+//      wins, and (1) pays one v_addc per mad.
+//      Checked against integers, one operation per lane on edge operands, for all eight fields: the host forms in
+//      tests/test_primitives_emu.py (and tests/cpp/field_check.cpp), the device forms in tests/test_gpu_primitives.py.
 //
 // Replaces ark-ff 0.3 `Fp256` (4x64 limbs) used by every reference call on the hot path
 // [REF barnett-smart-card-protocol/src/discrete_log_cards/mod.rs:7-8].

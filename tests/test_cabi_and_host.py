@@ -551,6 +551,14 @@ def test_bucket_msm_edge_scalars_under_emulation(emu, coracle):
     t.set_bucket_bits(0)
 
 
+@pytest.mark.parametrize("cvn", ["stark", "bn254", "secp256k1", "bls12_377"])
+def test_msm_on_exceptional_inputs_under_emulation(emu, coracle, cvn):
+    """duplicates, negatives and infinities under scalars whose partial sums cancel, Straus and bucket paths, every curve: the cases of
+    tests/test_gpu_parity.py::test_msm_on_exceptional_inputs (tests/prim_cases.py)"""
+    import prim_cases
+    assert prim_cases.run_msm_exceptional(emu(cvn), coracle, cvn) == 2 * 14 * 5
+
+
 @pytest.mark.parametrize("name", ["shuffle_stark_m3_n4_s11.json", "shuffle_stark_m4_n13_s9.json", "shuffle_secp256k1_m3_n3_s5.json"])
 def test_toom_cook_and_karatsuba_give_the_same_proof(emu, name):
     """3 <= m <= 8: the diagonals of the multi-exponentiation argument through Toom-Cook (2m products, evaluation at small integer

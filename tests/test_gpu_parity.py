@@ -670,6 +670,17 @@ def test_bucket_msm_large_and_edge_scalars(mp, coracle):
             assert got[64 * j:64 * j + 64] == coracle.msm(cv, sc[32 * K * j:32 * K * (j + 1)], bytes(pts)), (K, j)
 
 
+@pytest.mark.parametrize("cvn", ["stark", "bn254", "secp256k1", "bls12_377"])
+def test_msm_on_exceptional_inputs(mp, coracle, cvn):
+    """mp_msm on point sets full of duplicates, negatives and infinities, under scalars that make partial sums cancel (s and q - s on one
+    point, s on P and on -P, all scalars equal, 0 / 1 / q - 1, every term of a window in one bucket): the Straus path and the bucket path
+    at several window widths against the oracle's MSM, on every curve (tests/prim_cases.py; the same cases under the emulator in
+    tests/test_cabi_and_host.py)"""
+    import prim_cases
+    eng = mp.Engine(cvn, device=0)
+    assert prim_cases.run_msm_exceptional(eng, coracle, cvn) == 2 * 14 * 5
+
+
 @pytest.mark.parametrize("cvn,m,n,L,T,keyed", [("stark", 2, 26, 8, 40, True), ("stark", 4, 13, 3, 5, False), ("secp256k1", 2, 7, 4, 3, True),
                                                 ("stark", 8, 128, 2, 2, True),
                                                 ("stark", 2, 26, 32, 3, True)])     # BASELINE config 3 at its stated length: 32 players
