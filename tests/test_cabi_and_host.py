@@ -659,7 +659,7 @@ class _HostMem:
 
     def new(self, nbytes):
         import ctypes
-        buf = (ctypes.c_uint8 * max(nbytes, 1))()
+        buf = (ctypes.c_uint8 * max(nbytes, 1)).from_buffer_copy(b"\x5a" * max(nbytes, 1))      # (as _TorchMem: zeroing is observed)
         return buf, ctypes.addressof(buf)
 
     def get(self, h, nbytes):
@@ -674,6 +674,45 @@ def test_emulated_device_decompression_matches_oracle(emu, name):
     from decompress_cases import run_decompress_cases
     g = load_json(os.path.join(GOLDEN, name))
     run_decompress_cases(emu(g["curve"]), _HostMem(), g["curve"], g, n_random=6 if g["curve"] != "bls12_377" else 3)
+
+
+@pytest.mark.parametrize("curve", ["stark", "bn254", "secp256k1", "bls12_377"])
+def test_emulated_device_decompression_structured_pool(emu, curve):
+    """the kernel body of k_decompress under emulation on the structured pool (tests/decompress_pool.py): every family -- prescribed first
+    non-zero window, digit patterns, non-residues with a root, y at the limb boundaries of the sign rule, x at every edge, torsion --
+    in launches of 1, 63, 64, 65 points and of the whole pool, then the u64 length prefix and the small deck shapes.  On BLS12-377
+    families a and b are not observable (cofactor; decompress_pool.py) and the digit pairs come from 200 random subgroup points.  Calls
+    beyond one launch of 2^20 points run on the GPU only (tests/test_gpu_decompress.py)"""
+    import decompress_cases as dc
+    import decompress_pool as dp
+    pool = dp.pool(curve)
+    dp.assert_coverage(curve, pool)
+    eng = emu(curve)
+    dc.run_pool_launches(eng, _HostMem(), curve, pool)
+    dc.run_framing_cases(eng, _HostMem(), curve, pool)
+
+
+def test_emulated_points_across_launches(emu):
+    """a call of 2^20 + 1 points is cut into two launches (a.first, a.lanes in decompress_device): the secp256k1 pool, refused cases
+    included, tiled over the call.  secp256k1 because its square root is one exponentiation (S = 1): a million points take seconds here;
+    it has no scratch chain, so the scratch stride across launches, three launches and decks across a launch boundary are checked on
+    the GPU only (tests/test_gpu_decompress.py)"""
+    import decompress_cases as dc
+    import decompress_pool as dp
+    dc.run_tiled_points(emu("secp256k1"), _HostMem(), "secp256k1", dp.pool("secp256k1"), (1 << 20) + 1)
+
+
+@pytest.mark.parametrize("curve", ["stark", "bn254", "secp256k1", "bls12_377"])
+def test_host_c_abi_structured_pool(native, curve):
+    """mp_points_deserialize / mp_points_serialize / mp_deck_deserialize (host code of the library, no device) on the structured pool:
+    fe_sqrt_host (Tonelli-Shanks) on right-hand sides of low and of odd order, compress_one's borrow chain on y at the limb boundaries.
+    Ser::points works on one thread below 16 points and strided over the host's threads from 16 on: refused points are placed at
+    indices on both sides of 16, and two of them at neighbouring indices, which different threads own"""
+    import decompress_cases as dc
+    import decompress_pool as dp
+    pool = dp.pool(curve)
+    dp.assert_coverage(curve, pool)
+    dc.run_host_cases(native.Serializer(curve), native.NativeError, curve, pool)
 
 
 @pytest.mark.parametrize("cv,keyed", [("stark", False), ("stark", True), ("secp256k1", False)])

@@ -77,6 +77,37 @@ def test_infinity_and_errors():
         can.shuffle_proof_serialize("stark", 2, 26, bytes(10))
 
 
+def test_sign_limb_rule_matches_brute_force():
+    """decompress_pool.possible_diff_limbs (which limbs can decide `y > -y`: the coverage the sign-rule family is held to) against every y,
+    on small odd moduli cut into 2-bit limbs -- sparse ones like the STARK prime and all-ones ones like secp256k1's among them"""
+    import decompress_pool as dp
+    for p in (65, 97, 101, 129, 193, 251, 255, 257, 769, 1009, 1021):
+        for nw in (4, 5):
+            if p < 4 ** nw:
+                assert {dp.first_diff_limb(y, p, nw, 2) for y in range(1, p)} == dp.possible_diff_limbs(p, nw, 2), (p, nw)
+
+
+@pytest.mark.parametrize("curve", ["stark", "bn254", "secp256k1", "bls12_377"])
+def test_structured_pool_matches_oracle(curve):
+    """point_decompress / point_compress on the structured pool of tests/decompress_pool.py (right-hand sides of low and of odd order in
+    the 2-Sylow subgroup, non-residues with a root, y beside (p - 1) / 2, x at every edge, torsion on BLS12-377): the oracle's verdict
+    and bytes for every entry, the oracle's flag bit for every y"""
+    import decompress_pool as dp
+    import mp_oracle as po
+    cv = po.CURVES[curve]
+    pool = dp.pool(curve)
+    dp.assert_coverage(curve, pool)
+    for e in pool:
+        if e.ok:
+            assert can.point_decompress(curve, e.enc) == e.wire, e
+        else:
+            with pytest.raises(can.SerializationError):
+                can.point_decompress(curve, e.enc)
+        if e.P is not None:
+            with po.curve_ctx(cv):
+                assert can.point_compress(curve, po.pt_wire(e.P)) == e.enc, e
+
+
 def test_parameters_mirror_roundtrip():
     mp = importlib.import_module("mental-poker_amd")
     g = json.load(open(os.path.join(GOLDEN, "shuffle_stark_m2_n3_s1.json")))

@@ -223,6 +223,7 @@ class _TorchMem:
 
     def new(self, nbytes):
         t = self.torch.full((max(nbytes, 4),), 0x5A, dtype=self.torch.uint8, device=self.gpu)
+        self.torch.cuda.synchronize()      # the fill runs on torch's stream, the engine on its own: finish it before the engine zeroes
         return t, t.data_ptr()
 
     def get(self, h, nbytes):
