@@ -358,7 +358,7 @@ int mp_set_group_lanes(mp_table* t, uint32_t lanes);
  * E_k are the same group elements either way: proof bytes do not change.  Rebuilds the table's static plans. */
 int mp_set_toom_cook(mp_table* t, int on);
 /* Curves with a cofactor (MP_CURVE_BLS12_377): every wire point of a call -- decks, keys, proof elements -- is tested for
- * membership in the prime-order subgroup ([q]P == O), as ark-ec's validating deserialiser does; failures give
+ * membership in the prime-order subgroup ([q]P == O), as ark-ec's validating deserialiser does (the sigma calls included); failures give
  * MP_ERR_BAD_ENCODING for that proof.  on by default; a caller whose points were already validated (e.g. deserialised by
  * arkworks with checks) may switch it off -- it costs about three verifications per proof.  No effect on prime-order curves. */
 int mp_set_subgroup_check(mp_table* t, int on);
@@ -377,6 +377,11 @@ int mp_commit_batch(mp_table* t, size_t count, size_t len, const uint8_t* values
  * Per proof: bases g_i, publics a_i = x * g_i (nbases points each), witness x, `fs_init` = Blake2s digest of the bytes the
  * reference seeds its FiatShamirRng with (mp_blake2s of e.g. b"Masking Proof"), prover seed; proof = A_1..A_nb || z.
  * verify status: 0 Ok, 5 "Schnorr Identification", 6 "Chaum-Pedersen" [REF tests.rs:74-76,120,170], < 0 usage error.
+ * Wire points are validated like those of the shuffle calls: a base, a public or (verify) a commitment that is not canonical, not
+ * on the curve or -- on a curve with a cofactor, subject to mp_set_subgroup_check -- outside the prime-order subgroup gives
+ * MP_ERR_BAD_ENCODING for that proof, on the prover's side too (z g - c a - A = O also holds for a + L whenever c L = O, so without
+ * the test a key or a reveal token shifted by a low-order point L would be accepted with probability 1 / ord(L)).  A witness or a
+ * response >= q is MP_ERR_BAD_ENCODING as well.
  * The nonce is hedged ("sigma transcript v2"): r = Fr::rand(ChaCha20Rng(Blake2s(ToBytes(bases, publics) || Blake2s(witness || fs_init ||
  * prover_seed)))), so a repeated seed repeats the nonce only if witness and statement repeat too (the reference's `rng: &mut R` advances
  * by itself; an explicit seed does not).  Seeds should still be fresh CSPRNG output per call (`rng.fill_bytes`). */

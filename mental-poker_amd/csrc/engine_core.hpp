@@ -2107,6 +2107,9 @@ struct Table : mp_table {
     MP_RUN(k_load_points, C, B, nb, lg);
     LoadPointsArgs la{da.p, w.P.p, w.status.p, w.Bpad, nb, l.a};
     MP_RUN(k_load_points, C, B, nb, la);
+    // wire points are validated like those of the shuffle calls (mp_set_subgroup_check): z g - c a - A = O also holds for a + L
+    // whenever c L = O, so a key or a reveal token shifted by a low-order point would pass with probability 1 / ord(L)
+    check_subgroup(w, B, l.g, 2 * nb);      // bases and publics are consecutive P slots
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     if (prove) {
       dx.alloc((size_t)B * 32, s, false); dseed.alloc((size_t)B * 32, s, false);
@@ -2126,6 +2129,7 @@ struct Table : mp_table {
       rt::h2d(dpf.p, proofs, (size_t)B * psz, s);
       SigmaIoArgs io{dpf.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
       MP_RUN(k_sigma_load, C, B, nb + 1, io);
+      check_subgroup(w, B, l.A, nb);
       SigmaFsArgs fa{f, w.S.p, w.P.p, dfs.p, l, 0};
       MP_RUN(k_sigma_fs, C, B, 1, fa);
       run_phase(ad.dev, w, B);

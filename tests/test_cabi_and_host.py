@@ -365,6 +365,57 @@ def test_emulated_sigma_engine_matches_oracle(emu):
     t.close()
 
 
+_CURVES = ["stark", "bn254", "secp256k1", "bls12_377"]
+
+
+@pytest.mark.parametrize("cvn", _CURVES)
+def test_emulated_sigma_batches_match_oracle(emu, coracle, cvn):
+    """k_sigma_init / _fs / _store / _load / _verdict on every curve, one and two bases, batches of 1, 63, 64, 65 and 257: witnesses 0, 1,
+    2, q - 1, (q +- 1) / 2, equal and opposite bases, a transcript seed per lane -- the oracle's bytes, lane by lane
+    (tests/trait_cases.py; the same cases on the GPU: tests/test_gpu_protocol.py)"""
+    import trait_cases
+    fails, checks = trait_cases.run_sigma_honest(emu(cvn), coracle, cvn)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 2 * (3 * 450 + 4 + 65)      # prove, oracle and verify per lane; the shared-seed pair; the Python oracle's batch
+
+
+@pytest.mark.parametrize("cvn", _CURVES)
+def test_emulated_sigma_rejections_match_oracle(emu, coracle, cvn):
+    """one defect per lane between honest lanes (response, commitments, publics, bases, transcript seed, points off the curve): the
+    oracle's verdict for that lane and no other; the prover refuses a witness >= q and a bad base, and only those lanes"""
+    import trait_cases
+    fails, checks = trait_cases.run_sigma_rejections(emu(cvn), coracle, cvn)
+    assert not fails, "\n".join(fails[:20])
+    assert checks >= 40
+
+
+def test_emulated_sigma_calls_test_subgroup_membership(emu, coracle):
+    """BLS12-377: a base, a public or a commitment on the curve and outside the prime-order subgroup is a bad encoding for the sigma
+    calls as it is for the shuffle calls, unless mp_set_subgroup_check says that the caller has validated its points"""
+    import trait_cases
+    fails, checks = trait_cases.run_sigma_subgroup(emu("bls12_377"), coracle)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 19 + 16 + 19
+
+
+@pytest.mark.parametrize("cvn", _CURVES)
+def test_emulated_remask_batch_matches_oracle(emu, coracle, cvn):
+    """mp_remask_batch on 1, 63, 65 and 257 cards: edge factors, halves at infinity, the card (G, pk) doubled and cancelled"""
+    import trait_cases
+    fails, checks = trait_cases.run_remask(emu(cvn), coracle, cvn)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 1 + 63 + 65 + 257
+
+
+@pytest.mark.parametrize("cvn", _CURVES)
+def test_emulated_commit_batch_matches_oracle(emu, coracle, cvn):
+    """mp_commit_batch: full, short, single-value and empty rows, edge values and blinders, the all-zero row"""
+    import trait_cases
+    fails, checks = trait_cases.run_commit(emu(cvn), coracle, cvn)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 1 + 1 + 5 + 65 + 3
+
+
 @pytest.mark.parametrize("cvn", ["stark", "bn254", "secp256k1", "bls12_377"])
 def test_setup_has_no_trapdoor_and_matches_oracle(emu, cvn):
     """mp_setup ("setup v2"): n + 3 independent `C::rand` points (x from the stream, lifted, cofactor-cleared) -- the same bytes as

@@ -1,24 +1,46 @@
 """-m gpu: the rest of the trait on the GPU, mirroring the reference's six non-shuffle tests
 [REF barnett-smart-card-protocol/src/discrete_log_cards/tests.rs:48-173; masking.rs:64-107; remasking.rs:65-114;
-reveal.rs:43-84] (same accept / reject behaviour and error names), with byte-for-byte parity against the oracle."""
+reveal.rs:43-84] (same accept / reject behaviour and error names), with byte-for-byte parity against the oracle.
+
+Everything here runs on all four curves: the DLCards flow (key generation, key ownership, aggregate key, mask, remask, reveal,
+unmask; M, N = 4, 13 on the STARK curve as in the reference, a smaller deck elsewhere -- the flow is one card), and the cases of
+tests/trait_cases.py, which the emulator tests of tests/test_cabi_and_host.py share: batched sigma proofs of one and two bases in
+batches of 1, 63, 64, 65 and 257 with edge witnesses and equal / opposite bases, one defect per lane of a verify batch, points outside
+the prime-order subgroup (BLS12-377), mp_remask_batch and mp_commit_batch on edge factors and points at infinity."""
 import pytest
 
 import mp_oracle as po
+import trait_cases
 
 pytestmark = pytest.mark.gpu
 
-CURVE = "stark"
-M, N_ = 4, 13          # the reference's test parameters [REF tests.rs:52-53]
+CURVES = trait_cases.CURVES
+SIZES = {"stark": (4, 13)}          # the reference's test parameters [REF tests.rs:52-53]; (2, 3) on the other curves
 
 
 @pytest.fixture(scope="module")
-def env(mp):
-    cards = mp.DLCards(CURVE, device=0)
-    pp = cards.setup(bytes(range(32)), M, N_)
-    cv = po.CURVES[CURVE]
-    opp = po.setup(cv, M, N_, po.ChaCha20Rng(bytes(range(32))))
-    assert pp.raw == po.params_to_bytes(opp)
-    return cards, pp, cv, opp
+def envs(mp):
+    cache = {}
+
+    def get(curve):
+        if curve not in cache:
+            M, N_ = SIZES.get(curve, (2, 3))
+            cards = mp.DLCards(curve, device=0)
+            pp = cards.setup(bytes(range(32)), M, N_)
+            cv = po.CURVES[curve]
+            opp = po.setup(cv, M, N_, po.ChaCha20Rng(bytes(range(32))))
+            assert pp.raw == po.params_to_bytes(opp)
+            cache[curve] = cards, pp, cv, opp
+        return cache[curve]
+    return get
+
+
+@pytest.fixture(params=CURVES)
+def env(request, envs):
+    """(cards, parameters, curve, the oracle's parameters); the body of a test that uses it runs with the oracle's encoders set to the curve"""
+    e = envs(request.param)
+    with po.curve_ctx(e[2]):
+        yield e
 
 
 def setup_players(mp, cards, pp, opp, cv, num):
@@ -28,7 +50,7 @@ def setup_players(mp, cards, pp, opp, cv, num):
         pk, sk = cards.player_keygen(rng, pp)
         opk, osk = po.player_keygen(opp, orng)
         assert sk == osk and pk == po.pt_wire(opk)
-        info = mp.fr_rand(CURVE, rng).to_bytes(32, "little")
+        info = mp.fr_rand(cards.curve, rng).to_bytes(32, "little")
         assert info == po.fe_bytes(po.fr_rand(cv, orng))
         players.append((pk, sk, info))
         agg = po.pt_add(cv, agg, opk)
@@ -43,7 +65,7 @@ def test_generate_and_verify_key(mp, env):
     proof = cards.prove_key_ownership(b"\x05" * 32, pp, pk, sk, info)
     assert proof == po.sigma_proof_bytes(po.prove_key_ownership(opp, po.pt_from_wire(pk), sk, info, b"\x05" * 32))
     assert cards.verify_key_ownership(pp, pk, info, proof) is None
-    wrong_sk = mp.fr_rand(CURVE, rng)
+    wrong_sk = mp.fr_rand(cards.curve, rng)
     wrong_proof = cards.prove_key_ownership(b"\x05" * 32, pp, pk, wrong_sk, info)
     with pytest.raises(mp.CryptoError) as e:
         cards.verify_key_ownership(pp, pk, info, wrong_proof)
@@ -56,7 +78,7 @@ def test_aggregate_keys(mp, env):
     triples = [(pk, cards.prove_key_ownership(bytes([i]) * 32, pp, pk, sk, info), info) for i, (pk, sk, info) in enumerate(players)]
     assert cards.compute_aggregate_key(pp, triples) == expected
     bad = list(triples)
-    bad[3] = (bytes(64), bad[3][1], bad[3][2])          # a zeroed key [REF tests.rs:108-115]
+    bad[3] = (bytes(cards.engine.point_bytes), bad[3][1], bad[3][2])          # a zeroed key [REF tests.rs:108-115]
     with pytest.raises(mp.CardProtocolError) as e:
         cards.compute_aggregate_key(pp, bad)
     assert e.value == mp.CardProtocolError("ProofVerificationError", mp.CryptoError("Schnorr Identification"))
@@ -67,9 +89,9 @@ def test_verify_masking_remasking_reveal_unmask(mp, env):
     players, agg = setup_players(mp, cards, pp, opp, cv, 10)
     oagg = po.pt_from_wire(agg)
     rng = mp.ChaCha20Rng(b"\x31" * 32)
-    card_pt = po.pt_mul(cv, mp.fr_rand(CURVE, rng), cv.G)
+    card_pt = po.pt_mul(cv, mp.fr_rand(cards.curve, rng), cv.G)
     card = po.pt_wire(card_pt)
-    r = mp.fr_rand(CURVE, rng)
+    r = mp.fr_rand(cards.curve, rng)
     # test_verify_masking [REF masking.rs:64-107]
     masked, proof = cards.mask(b"\x41" * 32, pp, agg, card, r)
     omasked, oproof = po.mask(opp, oagg, card_pt, r, b"\x41" * 32)
@@ -80,7 +102,7 @@ def test_verify_masking_remasking_reveal_unmask(mp, env):
         cards.verify_mask(pp, agg, card, wrong_masked, proof)
     assert e.value == mp.CryptoError("Chaum-Pedersen")
     # test_verify_remasking [REF remasking.rs:65-114]
-    alpha = mp.fr_rand(CURVE, rng)
+    alpha = mp.fr_rand(cards.curve, rng)
     remasked, rproof = cards.remask(b"\x42" * 32, pp, agg, masked, alpha)
     oremasked, orproof = po.remask_with_proof(opp, oagg, omasked, alpha, b"\x42" * 32)
     assert remasked == po.deck_to_bytes([oremasked]) and rproof == po.sigma_proof_bytes(orproof)
@@ -107,9 +129,9 @@ def test_verify_masking_remasking_reveal_unmask(mp, env):
     assert e.value == mp.CardProtocolError("ProofVerificationError", mp.CryptoError("Chaum-Pedersen"))
 
 
-def test_sigma_batch_parity(mp, env):
+def test_sigma_batch_parity(mp, envs):
     """a batch of 64 Chaum-Pedersen proofs through the C ABI equals the oracle; one tampered proof fails alone"""
-    cards, pp, cv, opp = env
+    cards, pp, cv, opp = envs("stark")
     t = cards.table(pp, pp.enc_parameters)
     rng = po.ChaCha20Rng(b"\x61" * 32)
     B = 64
@@ -132,3 +154,38 @@ def test_sigma_batch_parity(mp, env):
     bad[17 * 160 + 159] ^= 1
     st = t.sigma_verify_batch(2, bases, pubs, bytes(bad), fsi)
     assert st[17] == 6 and sum(1 for v in st if v) == 1
+
+
+# ---- the cases of tests/trait_cases.py on the gfx950 build (the emulator runs the same ones: tests/test_cabi_and_host.py) ------------
+@pytest.mark.parametrize("curve", CURVES)
+def test_sigma_batches_match_oracle(envs, coracle, curve):
+    fails, checks = trait_cases.run_sigma_honest(envs(curve)[0].engine, coracle, curve)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 2 * (3 * 450 + 4 + 65)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_sigma_rejections_match_oracle(envs, coracle, curve):
+    fails, checks = trait_cases.run_sigma_rejections(envs(curve)[0].engine, coracle, curve)
+    assert not fails, "\n".join(fails[:20])
+    assert checks >= 40
+
+
+def test_sigma_calls_test_subgroup_membership(envs, coracle):
+    fails, checks = trait_cases.run_sigma_subgroup(envs("bls12_377")[0].engine, coracle)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 19 + 16 + 19
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_remask_batch_matches_oracle(envs, coracle, curve):
+    fails, checks = trait_cases.run_remask(envs(curve)[0].engine, coracle, curve)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 1 + 63 + 65 + 257
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_commit_batch_matches_oracle(envs, coracle, curve):
+    fails, checks = trait_cases.run_commit(envs(curve)[0].engine, coracle, curve)
+    assert not fails, "\n".join(fails[:20])
+    assert checks == 1 + 1 + 5 + 65 + 3
