@@ -110,6 +110,51 @@ class DLCardsT {
     return proof;
   }
 
+  // Opening cards in batches (mpshuffle.h "opening cards"): compute_reveal_token / unmask [REF mod.rs:300-378] for the T tokens of
+  // many cards in one call each.  signer[c T + j] = index into keys of the player whose token j of card c is; tokens, proofs and
+  // status words come in that order.  Pass-throughs on the table of (pp, shared_key): status words are returned, not thrown.
+  typedef PublicKey RevealToken;
+  typedef std::array<uint8_t, 2 * PB + 32> ZKProofReveal;
+  struct RevealedTokens {
+    std::vector<RevealToken> tokens;
+    std::vector<ZKProofReveal> proofs;
+    std::vector<int32_t> status;
+  };
+  struct OpenedCards {
+    std::vector<PublicKey> plaintexts;          // c1 - sum of the card's tokens; zero bytes for a card that was not opened
+    std::vector<uint32_t> index;                // place in card_list, 0xFFFFFFFF = not there
+    std::vector<int32_t> token_status, card_status;
+  };
+  RevealedTokens compute_reveal_tokens(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const PublicKey& shared_key,
+                                       const std::vector<PublicKey>& keys, const std::vector<std::array<uint8_t, 32>>& secret_keys,
+                                       const std::vector<MaskedCard>& cards, const std::vector<uint32_t>& signer) {
+    if (cards.empty() || signer.empty() || signer.size() % cards.size() || keys.empty() || secret_keys.size() != keys.size() ||
+        rng_seeds.size() != signer.size())
+      throw CardProtocolError("compute_reveal_tokens: the same number of signers for every card, one seed per token, one secret per key");
+    bind(pp, shared_key);
+    RevealedTokens r{std::vector<RevealToken>(signer.size()), std::vector<ZKProofReveal>(signer.size()), std::vector<int32_t>(signer.size())};
+    if (mp_reveal_batch(table_, keys.size(), keys[0].data(), secret_keys[0].data(), cards.size(), cards[0].data(),
+                        (uint32_t)(signer.size() / cards.size()), signer.data(), rng_seeds[0].data(), r.tokens[0].data(), r.proofs[0].data(),
+                        r.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return r;
+  }
+  OpenedCards open_cards(const Parameters& pp, const PublicKey& shared_key, const std::vector<PublicKey>& keys, const std::vector<MaskedCard>& cards,
+                         const std::vector<uint32_t>& signer, const std::vector<RevealToken>& tokens, const std::vector<ZKProofReveal>& proofs,
+                         const std::vector<PublicKey>& card_list) {
+    if (cards.empty() || signer.empty() || signer.size() % cards.size() || keys.empty() || tokens.size() != signer.size() ||
+        proofs.size() != signer.size())
+      throw CardProtocolError("open_cards: the same number of signers for every card, one token and one proof per signer");
+    bind(pp, shared_key);
+    OpenedCards o{std::vector<PublicKey>(cards.size()), std::vector<uint32_t>(cards.size()), std::vector<int32_t>(signer.size()),
+                  std::vector<int32_t>(cards.size())};
+    if (mp_unmask_batch(table_, keys.size(), keys[0].data(), cards.size(), cards[0].data(), (uint32_t)(signer.size() / cards.size()),
+                        signer.data(), tokens[0].data(), proofs[0].data(), card_list.size(), card_list.empty() ? nullptr : card_list[0].data(),
+                        o.plaintexts[0].data(), o.index.data(), o.token_status.data(), o.card_status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return o;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
 
  private:

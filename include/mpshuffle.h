@@ -392,6 +392,37 @@ int mp_sigma_verify_batch(mp_table* t, size_t B, uint32_t nbases, const uint8_t*
                           const uint8_t* proofs, const uint8_t* fs_init, int32_t* status);
 int mp_blake2s(const uint8_t* in, size_t len, uint8_t out[32]);   /* host helper: BLAKE2s-256 */
 
+/* ---- opening cards in batches: reveal tokens with their proofs, and unmasking [REF mod.rs:300-378; examples/round.rs:159-206, 352-430]
+ * After the shuffles every card that is looked at or shown takes one reveal token with a Chaum-Pedersen proof from each player, and
+ * whoever opens the card verifies the proofs and computes c1 - sum of the tokens.  One call carries the cards of many tables:
+ *   keys     K wire points: the players' public keys of all tables of the call        cards    C masked cards (c0 || c1)
+ *   T        tokens per card                                                          signer   C x T uint32: signer[c T + j] = index into
+ *   keys of the player whose token j of card c is; everything per token is in the lane order c T + j.
+ * mp_reveal_batch (a player): token = secret_keys[signer] * c0 with the "sigma transcript v2" proof for the bases (c0, G), the publics
+ * (token, keys[signer]) and fs_init = Blake2s("Reveal Proof") -- the bytes of mp_msm followed by mp_sigma_prove_batch on those inputs, one
+ * window table of c0 for token and commitment.  secret_keys: K scalars in the order of keys (pk = sk * G is NOT checked, as in the
+ * reference: such a proof does not verify); prover_seeds: C x T x 32 fresh random bytes; status[c T + j]: 0 or < 0.
+ * mp_unmask_batch (whoever opens): token_status[c T + j] = 0, 6 "Chaum-Pedersen", MP_ERR_BAD_ENCODING (token, key, card point or
+ * commitment not canonical, not on the curve or -- subject to mp_set_subgroup_check -- outside the prime-order subgroup; response >= q)
+ * or MP_ERR_BAD_ARGUMENT (signer >= K); card_status[c] = the first token_status of the card that is not 0, in j order (the reference
+ * fails at the first bad token).  A card with status 0: out_plain[c] = c1 - sum_j token as a canonical wire point and out_index[c] = the
+ * smallest i with plain_cards[i] == out_plain[c] as bytes, or 0xFFFFFFFF; any other card: zero bytes and 0xFFFFFFFF.  The tokens of a
+ * card are summed as given: that they come from distinct players, or from all of them, is the caller's to check, as in the reference.
+ * plain_cards: n_plain <= 4 096 wire points (NULL if 0), validated once per call as encodings: a bad one is MP_ERR_BAD_ENCODING for the call.
+ * Limits: 1 <= T, C * T <= 1 048 576, 1 <= K <= 1 048 576 (MP_ERR_BAD_ARGUMENT otherwise).  Keyed and keyless tables alike (of the
+ * parameters only G is used); never coalesced.
+ * mp_unmask_batch_dev: the same with every pointer a DEVICE pointer -- d_cards may be the d_out_decks of the prover -- enqueued on the
+ * context's stream; the outputs are final after mp_sync.  (With n_plain > 0 the call waits once for the stream and reads the card list
+ * back to validate it.)  The buffers stay untouched until then. */
+int mp_reveal_batch(mp_table* t, size_t K, const uint8_t* keys, const uint8_t* secret_keys, size_t C, const uint8_t* cards, uint32_t T,
+                    const uint32_t* signer, const uint8_t* prover_seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status);
+int mp_unmask_batch(mp_table* t, size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
+                    const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain_cards, uint8_t* out_plain,
+                    uint32_t* out_index, int32_t* token_status, int32_t* card_status);
+int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, const void* d_cards, uint32_t T, const void* d_signer,
+                        const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards, void* d_out_plain,
+                        void* d_out_index, void* d_token_status, void* d_card_status);
+
 /* ---- canonical serialisation (arkworks-0.3 `CanonicalSerialize` / `CanonicalDeserialize`, compressed) ----------------------
  * Every associated type of the trait is CanonicalSerialize + CanonicalDeserialize [REF src/lib.rs:45-71], and the reference's
  * harness measures `proof.serialized_size()` [REF examples/parameter_selection.rs:95]: these are the conversions between those

@@ -24,7 +24,7 @@ SYMBOLS = [
     "mp_shuffle_and_remask_batch", "mp_verify_shuffle_batch", "mp_shuffle_and_remask_batch_dev",
     "mp_verify_shuffle_batch_dev", "mp_verify_shuffle_chain", "mp_verify_shuffle_chain_dev", "mp_sync", "mp_reserve", "mp_set_latency_batch", "mp_remask_batch", "mp_msm", "mp_commit_batch",
     "mp_profile_enable", "mp_profile_report", "mp_work_census", "mp_plan_stats", "mp_sigma_prove_batch",
-    "mp_sigma_verify_batch", "mp_blake2s",
+    "mp_sigma_verify_batch", "mp_blake2s", "mp_reveal_batch", "mp_unmask_batch", "mp_unmask_batch_dev",
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
@@ -238,6 +238,9 @@ def bind(cdll):
     cdll.mp_sigma_prove_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, u8p, u8p, u8p, i32p]
     cdll.mp_sigma_verify_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, u8p, i32p]
     cdll.mp_blake2s.argtypes = [u8p, c.c_size_t, u8p]
+    cdll.mp_reveal_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_unmask_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, c.c_size_t, u8p, u8p, u32p, i32p, i32p]
+    cdll.mp_unmask_batch_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint32] + [c.c_void_p] * 3 + [c.c_size_t] + [c.c_void_p] * 5
     for fn, at in (("mp_serialized_point_size", [c.c_int]), ("mp_serialized_deck_size", [c.c_int, c.c_size_t]),
                    ("mp_serialized_params_size", [c.c_int, c.c_uint32]), ("mp_serialized_proof_size", [c.c_int, c.c_uint32, c.c_uint32])):
         getattr(cdll, fn).argtypes = at
@@ -664,6 +667,52 @@ class Table:
         st = (ctypes.c_int32 * B)()
         self.eng._chk(self.lib.mp_sigma_verify_batch(self.h, B, nbases, _in(bases), _in(publics), _in(proofs), _in(fs_init), st))
         return list(st)
+
+    # ---- opening cards: K keys, C cards, T tokens per card; signer: C * T indices into the keys, lane order c * T + j
+    NO_INDEX = 0xFFFFFFFF
+
+    def reveal_batch(self, keys, secret_keys, cards, T, signer, seeds):
+        """a player's side: token = sk[signer] * c0 with its Chaum-Pedersen proof, per (card, token) -> (tokens, proofs, status)"""
+        K, C = len(keys) // self.pb, len(cards) // self.cb
+        B = C * T
+        self._need("keys", len(keys), K * self.pb)
+        self._need("secret keys", len(secret_keys), K * 32)
+        self._need("cards", len(cards), C * self.cb)
+        self._need("signer", len(signer), B)
+        self._need("prover seeds", len(seeds), B * 32)
+        tok = (ctypes.c_uint8 * max(B * self.pb, 1))()
+        prf = (ctypes.c_uint8 * max(B * (2 * self.pb + 32), 1))()
+        st = (ctypes.c_int32 * max(B, 1))()
+        sg = (ctypes.c_uint32 * max(B, 1))(*signer)
+        self.eng._chk(self.lib.mp_reveal_batch(self.h, K, _in(keys), _in(secret_keys), C, _in(cards), T, sg, _in(seeds), tok, prf, st))
+        return bytes(tok)[:B * self.pb], bytes(prf)[:B * (2 * self.pb + 32)], list(st)[:B]
+
+    def unmask_batch(self, keys, cards, T, signer, tokens, proofs, plain_cards=b""):
+        """whoever opens: verify every token, plaintext = c1 - sum of the card's tokens, index of the plaintext in plain_cards
+        -> (plaintexts, indices, token_status, card_status)"""
+        K, C = len(keys) // self.pb, len(cards) // self.cb
+        B = C * T
+        n_plain = len(plain_cards) // self.pb
+        self._need("keys", len(keys), K * self.pb)
+        self._need("cards", len(cards), C * self.cb)
+        self._need("signer", len(signer), B)
+        self._need("tokens", len(tokens), B * self.pb)
+        self._need("proofs", len(proofs), B * (2 * self.pb + 32))
+        self._need("card list", len(plain_cards), n_plain * self.pb)
+        out = (ctypes.c_uint8 * max(C * self.pb, 1))()
+        idx = (ctypes.c_uint32 * max(C, 1))()
+        ts = (ctypes.c_int32 * max(B, 1))()
+        cs = (ctypes.c_int32 * max(C, 1))()
+        sg = (ctypes.c_uint32 * max(B, 1))(*signer)
+        self.eng._chk(self.lib.mp_unmask_batch(self.h, K, _in(keys), C, _in(cards), T, sg, _in(tokens), _in(proofs), n_plain,
+                                               _in(plain_cards) if n_plain else None, out, idx, ts, cs))
+        return bytes(out)[:C * self.pb], list(idx)[:C], list(ts)[:B], list(cs)[:C]
+
+    def unmask_batch_dev(self, K, d_keys, C, d_cards, T, d_signer, d_tokens, d_proofs, n_plain, d_plain_cards, d_out_plain, d_out_index,
+                         d_token_status, d_card_status):
+        """the same with device pointers (d_cards may be the prover's d_out_decks); outputs are final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_unmask_batch_dev(self.h, K, d_keys, C, d_cards, T, d_signer, d_tokens, d_proofs, n_plain, d_plain_cards,
+                                                   d_out_plain, d_out_index, d_token_status, d_card_status))
 
     def set_io_chunk(self, proofs):
         """proofs per pipelined chunk of the host-buffer entry points (0 = default 65536)"""

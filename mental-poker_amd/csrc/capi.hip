@@ -1076,6 +1076,50 @@ int mp_sigma_verify_batch(mp_table* t, size_t B, uint32_t nbases, const uint8_t*
   MP_CATCH
 }
 
+// ---- opening cards: reveal tokens with their proofs, and unmasking (engine_core.hpp "opening cards")
+static const size_t OPEN_MAX_LANES = 1048576, OPEN_MAX_KEYS = 1048576, OPEN_MAX_CARD_LIST = 4096;
+static bool open_shape_ok(size_t K, size_t C, uint32_t T) {
+  return K >= 1 && K <= OPEN_MAX_KEYS && C >= 1 && C <= OPEN_MAX_LANES && T >= 1 && T <= OPEN_MAX_LANES && C * (size_t)T <= OPEN_MAX_LANES;
+}
+int mp_reveal_batch(mp_table* t, size_t K, const uint8_t* keys, const uint8_t* secret_keys, size_t C, const uint8_t* cards, uint32_t T,
+                    const uint32_t* signer, const uint8_t* prover_seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) {
+  if (!t || !keys || !secret_keys || !cards || !signer || !prover_seeds || !out_tokens || !out_proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_reveal_batch: null argument");
+  if (!open_shape_ok(K, C, T)) return fail(MP_ERR_BAD_ARGUMENT, "mp_reveal_batch: 1 <= T, C * T <= 1 048 576, 1 <= K <= 1 048 576");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->reveal_host(K, keys, secret_keys, C, cards, T, signer, prover_seeds, out_tokens, out_proofs, status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_unmask_batch(mp_table* t, size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
+                    const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain_cards, uint8_t* out_plain,
+                    uint32_t* out_index, int32_t* token_status, int32_t* card_status) {
+  if (!t || !keys || !cards || !signer || !tokens || !proofs || (n_plain && !plain_cards) || !out_plain || !out_index || !token_status || !card_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_batch: null argument");
+  if (!open_shape_ok(K, C, T) || n_plain > OPEN_MAX_CARD_LIST)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_batch: 1 <= T, C * T <= 1 048 576, 1 <= K <= 1 048 576, n_plain <= 4 096");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  return t->unmask_host(K, keys, C, cards, T, signer, tokens, proofs, n_plain, plain_cards, out_plain, out_index, token_status, card_status);
+  MP_CATCH
+}
+int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, const void* d_cards, uint32_t T, const void* d_signer,
+                        const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards, void* d_out_plain,
+                        void* d_out_index, void* d_token_status, void* d_card_status) {
+  if (!t || !d_keys || !d_cards || !d_signer || !d_tokens || !d_proofs || (n_plain && !d_plain_cards) || !d_out_plain || !d_out_index ||
+      !d_token_status || !d_card_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_batch_dev: null argument");
+  if (!open_shape_ok(K, C, T) || n_plain > OPEN_MAX_CARD_LIST)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_batch_dev: 1 <= T, C * T <= 1 048 576, 1 <= K <= 1 048 576, n_plain <= 4 096");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  return t->unmask_dev(K, (const uint8_t*)d_keys, C, (const uint8_t*)d_cards, T, (const uint32_t*)d_signer, (const uint8_t*)d_tokens,
+                       (const uint8_t*)d_proofs, n_plain, (const uint8_t*)d_plain_cards, (uint8_t*)d_out_plain, (uint32_t*)d_out_index,
+                       (int32_t*)d_token_status, (int32_t*)d_card_status);
+  MP_CATCH
+}
+
 int mp_plan_stats(mp_table* t, uint64_t out[16]) {
   if (!t || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_plan_stats: bad argument");
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);

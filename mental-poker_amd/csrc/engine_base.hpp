@@ -257,6 +257,16 @@ struct mp_table {
   virtual void commit_host(size_t count, size_t len, const uint8_t* values, const uint8_t* r, uint8_t* out) = 0;
   virtual void sigma_host(bool prove, size_t B, uint32_t nb, const uint8_t* bases, const uint8_t* publics, const uint8_t* witness,
                           const uint8_t* fs_init, const uint8_t* seeds, uint8_t* proofs, int32_t* status) = 0;
+  // opening cards (kernels_open.hpp): K keys, C cards, T tokens per card, lane c * T + j; reveal_host / unmask_host take host
+  // buffers, unmask_dev device pointers.  unmask_*: MP_OK, or MP_ERR_BAD_ENCODING for a bad entry of the card list
+  virtual void reveal_host(size_t K, const uint8_t* keys, const uint8_t* sks, size_t C, const uint8_t* cards, uint32_t T,
+                           const uint32_t* signer, const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) = 0;
+  virtual int unmask_host(size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
+                          const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain,
+                          uint32_t* out_index, int32_t* token_status, int32_t* card_status) = 0;
+  virtual int unmask_dev(size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
+                         const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain,
+                         uint32_t* out_index, int32_t* token_status, int32_t* card_status, bool plain_validated = false) = 0;
   virtual void census(uint64_t* pt, uint64_t* vt, uint64_t* po, uint64_t* vo) = 0;
   virtual void plan_stats(uint64_t out[16]) = 0;
 };

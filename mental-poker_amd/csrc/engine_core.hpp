@@ -5,6 +5,7 @@
 #include "kernels_bucket.hpp"
 #include "kernels_decompress.hpp"
 #include "kernels_sigma.hpp"
+#include "kernels_open.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
 
@@ -2136,6 +2137,218 @@ struct Table : mp_table {
       SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, nb == 1 ? 5 : 6};
       MP_RUN(k_sigma_verdict, C, B, 1, va);
     }
+    rt::d2h(status, w.status.p, (size_t)B * 4, s);
+    rt::stream_sync(s);
+  }
+
+  // ---------------------------------------------------------------- opening cards (kernels_open.hpp)
+  // Reveal tokens with their Chaum-Pedersen proofs, and their verification with the token sums and the card lookup, for the T tokens
+  // of C cards at once: lane b = c * T + j, the statement slots of kernels_sigma.hpp filled on the device (k_open_stmt).  Against
+  // sigma_host, which knows nothing about its statements: G is the table's fixed base (window table in HBM, no doubling chain), the
+  // commitments enter the checks as affine addends instead of terms with the scalar -1, and the prover builds the window table of c0
+  // once for token and commitment.  The plans are static and the workspace stays with the table: a device-resident call allocates
+  // nothing once it has seen its batch size.
+  struct OpenState {
+    bool ready = false;
+    Phase vph, rph1, rph2;          // checks of the verifier | the token x c0 | the commitments r c0, r G
+    PhaseDev vdev, rdev1, rdev2;
+    uint32_t nJ = 0, nD = 0, nT = 0;
+    uint32_t fs_seed[8];            // Blake2s("Reveal Proof")  [REF mod.rs:83]
+    Workspace w;
+    DevBuf<uint8_t> fs;             // [B][32]
+    DevBuf<uint32_t> c1, sumJ, sumP, scratch;      // the C-lane section: second halves of the cards, plaintexts
+    DevBuf<int32_t> cstat;
+  } op;
+  void open_prepare(uint32_t B) {
+    rt::Stream s = ctx->stream;
+    const SigmaLay l = make_sigma_lay(2);
+    if (!op.ready) {
+      FixedBases fb{n};
+      uint32_t np = l.chk + 2;
+      {
+        PhaseBuilder pb(op.vph, np, FCHUNK, VCHUNK);      // z g_i - c a_i - A_i, i = 0, 1
+        pb.begin(l.chk);
+        pb.var(l.z, l.g);
+        pb.var(l.negc, l.a);
+        pb.addend(l.A, true);
+        pb.end();
+        pb.begin(l.chk + 1);
+        pb.fixed(l.z, fb.G());
+        pb.var(l.negc, l.a + 1);
+        pb.addend(l.A + 1, true);
+        pb.end();
+      }
+      {
+        PhaseBuilder pb(op.rph1, np, FCHUNK, VCHUNK);
+        pb.begin(l.a);
+        pb.var(l.x, l.g);
+        pb.end();
+        pb.normalize(l.a, 1);
+      }
+      {
+        PhaseBuilder pb(op.rph2, np, FCHUNK, VCHUNK);
+        pb.begin(l.A);
+        pb.var(l.r, l.g);
+        pb.end();
+        pb.begin(l.A + 1);
+        pb.fixed(l.r, fb.G());
+        pb.end();
+        pb.normalize(l.A, 2);
+      }
+      // token and commitment share the base c0: both phases know its window table as table slot 0, and the first one builds it
+      if (op.rph1.tables.size() != 1 || op.rph2.tables.size() != 1 || op.rph1.tables[0].s != l.g || op.rph2.tables[0].s != l.g ||
+          op.rph1.tables[0].b != 0 || op.rph2.tables[0].b != 0)
+        throw std::logic_error("reveal plan: the phases do not share the table of c0");
+      op.rph2.tables.clear();
+      op.nJ = np;
+      for (const Phase* ph : {&op.vph, &op.rph1, &op.rph2}) {
+        op.nD = std::max(op.nD, ph->n_dslots);
+        op.nT = std::max(op.nT, ph->n_tslots);
+      }
+      op.vdev.upload(op.vph, s);
+      op.rdev1.upload(op.rph1, s);
+      op.rdev2.upload(op.rph2, s);
+      Blake2sState st;
+      blake2s_init(st);
+      uint32_t mblk[16] = {0};
+      memcpy(mblk, "Reveal Proof", 12);
+      blake2s_compress(st, mblk, 12, true);
+      memcpy(op.fs_seed, st.h, 32);
+      op.ready = true;
+    }
+    op.w.fw = G_::FW;
+    op.w.ensure(B, 6, 6, op.nJ, op.nD, op.nT, nwin, (6 * (G_::PB + 1) + 32) / 4 + 4, s);
+    op.fs.alloc((size_t)op.w.cap * 32, s, false);
+    rt::dzero(op.w.status.p, (size_t)op.w.Bpad * 4, s);
+  }
+  OpenStmtArgs open_stmt_args(size_t K, const uint8_t* keys, const uint8_t* cards, uint32_t T, const uint32_t* signer) {
+    OpenStmtArgs a{};
+    Workspace& w = op.w;
+    a.P = w.P.p; a.S = w.S.p; a.status = w.status.p;
+    a.keys = keys; a.cards = cards; a.signer = signer;
+    a.fbpts = fbpts.p;
+    a.fs_init = op.fs.p;
+    memcpy(a.fs_seed, op.fs_seed, 32);
+    a.l = make_sigma_lay(2);
+    a.Bpad = w.Bpad; a.K = (uint32_t)K; a.T = T; a.g_base = FixedBases{n}.G();
+    return a;
+  }
+  int check_card_list(size_t n_plain, const uint8_t* plain) {
+    for (size_t i = 0; i < n_plain; ++i) {
+      Aff<C> p;
+      if (!wire_point_host(plain + i * G_::PB, p))
+        return fail(MP_ERR_BAD_ENCODING, "card list: entry " + std::to_string(i) + " is not a canonical point of the curve");
+    }
+    return MP_OK;
+  }
+  // every pointer a device pointer; everything is enqueued on the context's stream.  (The card list is only ever compared with
+  // canonical bytes: it is validated as an encoding -- on the host, one short copy back unless the caller has done it -- and not
+  // tested for the subgroup.)
+  int unmask_dev(size_t K, const uint8_t* keys, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer, const uint8_t* tokens,
+                 const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain, uint32_t* out_index,
+                 int32_t* token_status, int32_t* card_status, bool plain_validated) override {
+    rt::Stream s = ctx->stream;
+    const uint32_t Cn = (uint32_t)C_, B = Cn * T;
+    if (n_plain && !plain_validated) {
+      std::vector<uint8_t> hp(n_plain * G_::PB);
+      rt::d2h(hp.data(), plain, hp.size(), s);
+      rt::stream_sync(s);
+      const int rc = check_card_list(n_plain, hp.data());
+      if (rc != MP_OK) return rc;
+    }
+    open_prepare(B);
+    Workspace& w = op.w;
+    const SigmaLay l = make_sigma_lay(2);
+    op.c1.alloc((size_t)Cn * G_::PW, s, false); op.sumJ.alloc((size_t)Cn * G_::JW, s, false); op.sumP.alloc((size_t)Cn * G_::PW, s, false);
+    op.scratch.alloc((size_t)Cn * G_::FW, s, false); op.cstat.alloc(Cn, s, false);
+    rt::dzero(op.cstat.p, (size_t)Cn * 4, s);
+    OpenStmtArgs sa = open_stmt_args(K, keys, cards, T, signer);
+    sa.tokens = tokens; sa.c1 = op.c1.p; sa.cstat = op.cstat.p;
+    MP_RUN(k_open_stmt, C, B, 4, sa);
+    SigmaIoArgs io{const_cast<uint8_t*>(proofs), w.S.p, w.P.p, w.status.p, l, w.Bpad};
+    MP_RUN(k_sigma_load, C, B, 3, io);
+    if (subgroup_check) {      // c0 | token, key | commitments (G is the table's own); c1 through the C-lane section
+      check_subgroup(w, B, l.g, 1);
+      check_subgroup(w, B, l.a, 4);      // publics and commitments are consecutive P slots
+      SubgroupArgs ca{op.c1.p, op.cstat.p, Cn, 0};
+      MP_RUN(k_subgroup_check, C, Cn, 1, ca);
+    }
+    const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+    SigmaFsArgs fa{f, w.S.p, w.P.p, op.fs.p, l, 0};
+    MP_RUN(k_sigma_fs, C, B, 1, fa);
+    run_phase(op.vdev, w, B);
+    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
+    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    UnmaskSumArgs ua{w.P.p, w.status.p, signer, op.c1.p, op.cstat.p, op.sumJ.p, token_status, card_status, w.Bpad, (uint32_t)K, T, l.a};
+    MP_RUN(k_unmask_sum, C, Cn, 1, ua);
+    normalize_flat(op.sumJ.p, op.sumP.p, op.scratch.p, Cn);
+    CardMatchArgs ma{op.sumP.p, card_status, plain, out_plain, out_index, (uint32_t)n_plain};
+    MP_RUN(k_card_match, C, Cn, 1, ma);
+    return MP_OK;
+  }
+  int unmask_host(size_t K, const uint8_t* keys, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer, const uint8_t* tokens,
+                  const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain, uint32_t* out_index,
+                  int32_t* token_status, int32_t* card_status) override {
+    rt::Stream s = ctx->stream;
+    const size_t B = C_ * T, psz = 2 * (size_t)G_::PB + 32;
+    const int rc = check_card_list(n_plain, plain);
+    if (rc != MP_OK) return rc;
+    DevBuf<uint8_t> dk, dc, dt, dp, dl, dout;
+    DevBuf<uint32_t> dsg, didx;
+    DevBuf<int32_t> dts, dcs;
+    dk.alloc(K * G_::PB, s, false); dc.alloc(C_ * 2 * G_::PB, s, false); dt.alloc(B * G_::PB, s, false); dp.alloc(B * psz, s, false);
+    dl.alloc(std::max<size_t>(n_plain * G_::PB, 4), s, false); dout.alloc(C_ * G_::PB, s, false);
+    dsg.alloc(B, s, false); didx.alloc(C_, s, false); dts.alloc(B, s, false); dcs.alloc(C_, s, false);
+    rt::h2d(dk.p, keys, K * G_::PB, s);
+    rt::h2d(dc.p, cards, C_ * 2 * G_::PB, s);
+    rt::h2d(dt.p, tokens, B * G_::PB, s);
+    rt::h2d(dp.p, proofs, B * psz, s);
+    rt::h2d(dsg.p, signer, B * 4, s);
+    if (n_plain) rt::h2d(dl.p, plain, n_plain * G_::PB, s);
+    unmask_dev(K, dk.p, C_, dc.p, T, dsg.p, dt.p, dp.p, n_plain, dl.p, dout.p, didx.p, dts.p, dcs.p, true);
+    rt::d2h(out_plain, dout.p, C_ * G_::PB, s);
+    rt::d2h(out_index, didx.p, C_ * 4, s);
+    rt::d2h(token_status, dts.p, B * 4, s);
+    rt::d2h(card_status, dcs.p, C_ * 4, s);
+    rt::stream_sync(s);
+    return MP_OK;
+  }
+  // token = sk[signer] c0 first: the hedged nonce hashes the whole statement, the token included (k_sigma_init)
+  void reveal_host(size_t K, const uint8_t* keys, const uint8_t* sks, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer,
+                   const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) override {
+    rt::Stream s = ctx->stream;
+    const uint32_t B = (uint32_t)(C_ * T);
+    const size_t psz = 2 * (size_t)G_::PB + 32;
+    open_prepare(B);
+    Workspace& w = op.w;
+    const SigmaLay l = make_sigma_lay(2);
+    DevBuf<uint8_t> dk, dx, dc, dseed, dtok, dpf;
+    DevBuf<uint32_t> dsg;
+    dk.alloc(K * G_::PB, s, false); dx.alloc(K * 32, s, false); dc.alloc(C_ * 2 * G_::PB, s, false); dseed.alloc((size_t)B * 32, s, false);
+    dtok.alloc((size_t)B * G_::PB, s, false); dpf.alloc((size_t)B * psz, s, false); dsg.alloc(B, s, false);
+    rt::h2d(dk.p, keys, K * G_::PB, s);
+    rt::h2d(dx.p, sks, K * 32, s);
+    rt::h2d(dc.p, cards, C_ * 2 * G_::PB, s);
+    rt::h2d(dseed.p, seeds, (size_t)B * 32, s);
+    rt::h2d(dsg.p, signer, (size_t)B * 4, s);
+    OpenStmtArgs sa = open_stmt_args(K, dk.p, dc.p, T, dsg.p);
+    sa.sks = dx.p;
+    MP_RUN(k_open_stmt, C, B, 4, sa);
+    check_subgroup(w, B, l.g, 1);          // c0 and the key, as the sigma calls test bases and publics (the token is computed here)
+    check_subgroup(w, B, l.a + 1, 1);
+    run_phase(op.rdev1, w, B);
+    const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+    SigmaInitArgs ia{w.S.p, dseed.p, l, w.Bpad, f, w.P.p, op.fs.p};
+    MP_RUN(k_sigma_init, C, B, 1, ia);
+    run_phase(op.rdev2, w, B);             // (its table list is empty: the table of c0 is the first phase's)
+    SigmaFsArgs fa{f, w.S.p, w.P.p, op.fs.p, l, 1};
+    MP_RUN(k_sigma_fs, C, B, 1, fa);
+    SigmaIoArgs io{dpf.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
+    MP_RUN(k_sigma_store, C, B, 3, io);
+    StorePointsArgs so{dtok.p, w.P.p, w.Bpad, 1, l.a};
+    MP_RUN(k_store_points, C, B, 1, so);
+    rt::d2h(out_tokens, dtok.p, (size_t)B * G_::PB, s);
+    rt::d2h(out_proofs, dpf.p, (size_t)B * psz, s);
     rt::d2h(status, w.status.p, (size_t)B * 4, s);
     rt::stream_sync(s);
   }

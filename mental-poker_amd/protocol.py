@@ -332,6 +332,65 @@ class DLCards:
                 raise CardProtocolError("ProofVerificationError", e)
         return self._mul(self._t(pp), [(1, masked_card[self.engine.point_bytes:])] + [(-1, tok) for tok, _, _ in decryption_key])
 
+    # -- opening cards in batches: compute_reveal_token / unmask for many cards and players in one call each (mp_reveal_batch,
+    #    mp_unmask_batch; statements, token sums and the card lookup run on the device)             [REF examples/round.rs:159-206, 352-430]
+    def _open_shape(self, n_keys, cards, signer):
+        pb = self.engine.point_bytes
+        if not cards or len(signer) % len(cards) or not signer or not n_keys:
+            raise CardProtocolError.io("signer must name the same number of players (at least one) for every card")
+        if any(len(bytes(c)) != 2 * pb for c in cards):
+            raise CardProtocolError.io("a card is %d bytes" % (2 * pb))
+        return len(signer) // len(cards)
+
+    def compute_reveal_tokens(self, rng_seeds, pp, players, cards, signer):
+        """players: [(pk, sk)]; cards: masked cards; signer[c * T + j]: index into players of whoever gives token j of card c;
+        rng_seeds: one fresh 32-byte seed per (card, token) -> [(RevealToken, ZKProofReveal)] in the order of signer"""
+        T = self._open_shape(len(players), cards, signer)
+        pb = self.engine.point_bytes
+        if len(rng_seeds) != len(signer) or any(len(bytes(s)) != 32 for s in rng_seeds):
+            raise CardProtocolError.io("one 32-byte prover seed per token")
+        if any(len(bytes(pk)) != pb for pk, _ in players) or any(not 0 <= int(g) < len(players) for g in signer):
+            raise CardProtocolError.io("a key is %d bytes, a signer an index into the players" % pb)
+        try:
+            tok, prf, st = self._t(pp).reveal_batch(b"".join(bytes(pk) for pk, _ in players), _scalar_bytes([sk for _, sk in players]),
+                                                    b"".join(bytes(c) for c in cards), T, [int(g) for g in signer],
+                                                    b"".join(bytes(s) for s in rng_seeds))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        bad = [v for v in st if v != 0]
+        if bad:
+            raise CardProtocolError.io(self.engine.check_name(bad[0]))
+        psz = 2 * pb + 32
+        return [(tok[l * pb:(l + 1) * pb], prf[l * psz:(l + 1) * psz]) for l in range(len(signer))]
+
+    def open_cards(self, pp, keys, cards, signer, tokens, proofs, card_list):
+        """keys: the players' public keys; signer / tokens / proofs: per (card, token) as compute_reveal_tokens orders them; card_list:
+        the plaintext cards to look the results up in.  -> per card (plaintext, index in card_list | None), or the error `unmask`
+        raises for it: CardProtocolError("ProofVerificationError", CryptoError("Chaum-Pedersen")) / CardProtocolError.io(...)"""
+        T = self._open_shape(len(keys), cards, signer)
+        pb = self.engine.point_bytes
+        psz = 2 * pb + 32
+        if len(tokens) != len(signer) or len(proofs) != len(signer) or any(len(bytes(t)) != pb for t in tokens) or \
+                any(len(bytes(p)) != psz for p in proofs) or any(len(bytes(k)) != pb for k in keys) or any(len(bytes(p)) != pb for p in card_list):
+            raise CardProtocolError.io("one %d-byte token and one %d-byte proof per signer; keys and listed cards are %d bytes" % (pb, psz, pb))
+        if any(not 0 <= int(g) < 1 << 32 for g in signer):
+            raise CardProtocolError.io("a signer is an index into the keys")
+        try:
+            plain, idx, _, cs = self._t(pp).unmask_batch(b"".join(bytes(k) for k in keys), b"".join(bytes(c) for c in cards), T,
+                                                         [int(g) for g in signer], b"".join(bytes(t) for t in tokens),
+                                                         b"".join(bytes(p) for p in proofs), b"".join(bytes(p) for p in card_list))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        out = []
+        for i, st in enumerate(cs):
+            if st > 0:
+                out.append(CardProtocolError("ProofVerificationError", CryptoError(self.engine.check_name(st))))
+            elif st < 0:
+                out.append(CardProtocolError.io(self.engine.check_name(st)))
+            else:
+                out.append((plain[i * pb:(i + 1) * pb], idx[i] if idx[i] != _native.Table.NO_INDEX else None))
+        return out
+
     # -- batched forms (the data-parallel axis: independent proofs of one table)
     def shuffle_and_remask_batch(self, rng_seeds, pp, shared_key, decks, masking_factors, permutations):
         t = self.table(pp, shared_key)
