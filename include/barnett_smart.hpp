@@ -155,9 +155,85 @@ class DLCardsT {
     return o;
   }
 
+  // Dealing and seating in batches (mpshuffle.h "dealing and seating"): mask / verify_mask / remask / verify_remask [REF mod.rs:182-298]
+  // for the cards of many tables, and compute_aggregate_key [REF mod.rs:167-180] for many tables, in one call each.  Card i goes under
+  // shared_keys[key_index[i]].  Pass-throughs on a table of pp (of the parameters only G is used): status words are returned, not thrown.
+  typedef std::array<uint8_t, 2 * PB + 32> ZKProofMasking;      // (ZKProofRemasking is the same type: a Chaum-Pedersen proof)
+  typedef std::array<uint8_t, PB + 32> ZKProofKeyOwnership;
+  struct DealtCards {
+    std::vector<MaskedCard> cards;              // zero bytes for a lane whose status is not 0
+    std::vector<ZKProofMasking> proofs;
+    std::vector<int32_t> status;
+  };
+  struct AggregateKeys {
+    std::vector<PublicKey> keys;                // zero bytes for a table whose status is not 0
+    std::vector<int32_t> player_status, table_status;
+  };
+  DealtCards deal(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const std::vector<PublicKey>& shared_keys,
+                  const std::vector<uint32_t>& key_index, const std::vector<PublicKey>& cards, const std::vector<Scalar>& factors) {
+    return mask_batch(MP_DEAL_MASK, rng_seeds, pp, shared_keys, key_index, cards.size(), cards.empty() ? nullptr : cards[0].data(), factors);
+  }
+  std::vector<int32_t> verify_deal(const Parameters& pp, const std::vector<PublicKey>& shared_keys, const std::vector<uint32_t>& key_index,
+                                   const std::vector<PublicKey>& cards, const std::vector<MaskedCard>& masked_cards,
+                                   const std::vector<ZKProofMasking>& proofs) {
+    return verify_mask_batch(MP_DEAL_MASK, pp, shared_keys, key_index, cards.size(), cards.empty() ? nullptr : cards[0].data(), masked_cards, proofs);
+  }
+  DealtCards deal_remask(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const std::vector<PublicKey>& shared_keys,
+                         const std::vector<uint32_t>& key_index, const std::vector<MaskedCard>& masked_cards, const std::vector<Scalar>& factors) {
+    return mask_batch(MP_DEAL_REMASK, rng_seeds, pp, shared_keys, key_index, masked_cards.size(),
+                      masked_cards.empty() ? nullptr : masked_cards[0].data(), factors);
+  }
+  std::vector<int32_t> verify_deal_remask(const Parameters& pp, const std::vector<PublicKey>& shared_keys, const std::vector<uint32_t>& key_index,
+                                          const std::vector<MaskedCard>& original_cards, const std::vector<MaskedCard>& remasked_cards,
+                                          const std::vector<ZKProofMasking>& proofs) {
+    return verify_mask_batch(MP_DEAL_REMASK, pp, shared_keys, key_index, original_cards.size(),
+                             original_cards.empty() ? nullptr : original_cards[0].data(), remasked_cards, proofs);
+  }
+  // tables x players, lane = table * players + seat; fs_init[lane] = Blake2s("Key Ownership Proof" || player_public_info) (mp_blake2s)
+  AggregateKeys compute_aggregate_keys(const Parameters& pp, size_t players, const std::vector<PublicKey>& keys,
+                                       const std::vector<ZKProofKeyOwnership>& proofs, const std::vector<std::array<uint8_t, 32>>& fs_init) {
+    if (!players || keys.empty() || keys.size() % players || proofs.size() != keys.size() || fs_init.size() != keys.size())
+      throw CardProtocolError("compute_aggregate_keys: the same number of players at every table, one proof and one digest per player");
+    bind_any(pp, keys[0]);
+    const size_t tables = keys.size() / players;
+    AggregateKeys a{std::vector<PublicKey>(tables), std::vector<int32_t>(keys.size()), std::vector<int32_t>(tables)};
+    if (mp_aggregate_keys_batch(table_, tables, (uint32_t)players, keys[0].data(), proofs[0].data(), fs_init[0].data(), a.keys[0].data(),
+                                a.player_status.data(), a.table_status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return a;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
 
  private:
+  DealtCards mask_batch(int kind, const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const std::vector<PublicKey>& shared_keys,
+                        const std::vector<uint32_t>& key_index, size_t count, const uint8_t* inputs, const std::vector<Scalar>& factors) {
+    if (!count || shared_keys.empty() || key_index.size() != count || factors.size() != count || rng_seeds.size() != count)
+      throw CardProtocolError("deal: at least one key and one card; one key index, one factor and one seed per card");
+    bind_any(pp, shared_keys[0]);
+    DealtCards d{std::vector<MaskedCard>(count), std::vector<ZKProofMasking>(count), std::vector<int32_t>(count)};
+    if (mp_mask_batch(table_, kind, shared_keys.size(), shared_keys[0].data(), count, key_index.data(), inputs, factors[0].data(),
+                      rng_seeds[0].data(), d.cards[0].data(), d.proofs[0].data(), d.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return d;
+  }
+  std::vector<int32_t> verify_mask_batch(int kind, const Parameters& pp, const std::vector<PublicKey>& shared_keys,
+                                         const std::vector<uint32_t>& key_index, size_t count, const uint8_t* inputs,
+                                         const std::vector<MaskedCard>& masked_cards, const std::vector<ZKProofMasking>& proofs) {
+    if (!count || shared_keys.empty() || key_index.size() != count || masked_cards.size() != count || proofs.size() != count)
+      throw CardProtocolError("verify_deal: at least one key and one card; one key index, one masked card and one proof per card");
+    bind_any(pp, shared_keys[0]);
+    std::vector<int32_t> status(count);
+    if (mp_verify_mask_batch(table_, kind, shared_keys.size(), shared_keys[0].data(), count, key_index.data(), inputs, masked_cards[0].data(),
+                             proofs[0].data(), status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return status;
+  }
+  // a table of pp, whatever its key: the calls that use only G of the parameters keep the one that is bound
+  void bind_any(const Parameters& pp, const PublicKey& pk) {
+    if (table_ && pp.raw == bound_params_ && pp.m == bound_m_) return;
+    bind(pp, pk);
+  }
   void bind(const Parameters& pp, const PublicKey& pk) {
     if (table_ && pp.raw == bound_params_ && pk == bound_pk_ && pp.m == bound_m_) return;
     if (table_) mp_table_destroy(table_);

@@ -423,6 +423,46 @@ int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, con
                         const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards, void* d_out_plain,
                         void* d_out_index, void* d_token_status, void* d_card_status);
 
+/* ---- dealing and seating in batches: masking / remasking with their proofs, and the tables' aggregate keys
+ * [REF mod.rs:151-298; examples/round.rs:228-262]
+ * Before the first shuffle every card of the open deck is masked with a Chaum-Pedersen proof and every player verifies all of them;
+ * before that, every player's key comes with a Schnorr proof and a table's aggregate key is the sum of its players' keys.  One call
+ * carries the cards, or the players, of many tables.  mask is remask of (O, card) [REF remasking.rs:10-22], so `kind` covers
+ * mask / verify_mask / remask / verify_remask:
+ *   MP_DEAL_MASK     inputs = C plaintext cards (one wire point each)     fs_init = Blake2s("Masking Proof")
+ *   MP_DEAL_REMASK   inputs = C masked cards (c0 || c1)                   fs_init = Blake2s("Remasking Proof")
+ *   keys       K wire points: the aggregate keys of the tables of the call      key_index  C uint32: key_index[c] < K names the key of card c
+ * mp_mask_batch (whoever deals): out_masked[c] = in + (r G, r pk) with in = (O, card) for MP_DEAL_MASK, and out_proofs[c] the "sigma
+ * transcript v2" proof for the bases (G, pk), the publics (r G, r pk) and the witness r = factors[c] -- the bytes of mp_msm / mp_remask_batch
+ * followed by mp_sigma_prove_batch on that statement; one window table of pk for r pk and the commitment.  prover_seeds: C x 32 fresh
+ * random bytes.  status[c]: 0, MP_ERR_BAD_ENCODING (key or input point not canonical, not on the curve or -- subject to
+ * mp_set_subgroup_check -- outside the prime-order subgroup; factor >= q) or MP_ERR_BAD_ARGUMENT (key_index >= K); a lane whose status is
+ * not 0 gives zero bytes.
+ * mp_verify_mask_batch (every player): the publics (masked.c0 - in.c0, masked.c1 - in.c1) are computed on the device; status[c] = the word
+ * of mp_sigma_verify_batch for that statement (0 or 6 "Chaum-Pedersen"), MP_ERR_BAD_ENCODING (key, input point, masked point or commitment
+ * not canonical, not on the curve or -- subject to mp_set_subgroup_check -- outside the subgroup; response >= q) or MP_ERR_BAD_ARGUMENT
+ * (key_index >= K, whatever else is wrong with the lane).
+ * Limits: 1 <= C, K <= 1 048 576 (MP_ERR_BAD_ARGUMENT for the call otherwise).  Keyed and keyless tables alike (of the parameters only G
+ * is used); never coalesced.
+ * mp_verify_mask_batch_dev: the same with every pointer a DEVICE pointer -- d_inputs may be the d_out_decks of a prover -- enqueued on the
+ * context's stream; d_status is final after mp_sync, and the buffers stay untouched until then.
+ * mp_aggregate_keys_batch (seating): `tables` tables of P players each, lane l = table * P + seat; keys, proofs (1 point + 1 scalar) and
+ * fs_init ([l][32] = Blake2s("Key Ownership Proof" || player_public_info), as mp_sigma_verify_batch takes it) per lane.  player_status[l] =
+ * the word of mp_sigma_verify_batch(nbases = 1) on (G, keys[l]): 0, 5 "Schnorr Identification" or MP_ERR_BAD_ENCODING; table_status[k] =
+ * the first player status of the table that is not 0, in seat order (the reference stops at the first bad proof); out_keys[k] = the sum of
+ * the table's keys as a canonical wire point if table_status[k] == 0, zero bytes otherwise.  The keys are summed as given: that they are
+ * distinct is the caller's to check, as in the reference.  Limits: 1 <= P, 1 <= tables, tables * P <= 1 048 576. */
+#define MP_DEAL_MASK 0
+#define MP_DEAL_REMASK 1
+int mp_mask_batch(mp_table* t, int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                  const uint8_t* factors, const uint8_t* prover_seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status);
+int mp_verify_mask_batch(mp_table* t, int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                         const uint8_t* masked, const uint8_t* proofs, int32_t* status);
+int mp_verify_mask_batch_dev(mp_table* t, int kind, size_t K, const void* d_keys, size_t C, const void* d_key_index, const void* d_inputs,
+                             const void* d_masked, const void* d_proofs, void* d_status);
+int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
+                            uint8_t* out_keys, int32_t* player_status, int32_t* table_status);
+
 /* ---- canonical serialisation (arkworks-0.3 `CanonicalSerialize` / `CanonicalDeserialize`, compressed) ----------------------
  * Every associated type of the trait is CanonicalSerialize + CanonicalDeserialize [REF src/lib.rs:45-71], and the reference's
  * harness measures `proof.serialized_size()` [REF examples/parameter_selection.rs:95]: these are the conversions between those

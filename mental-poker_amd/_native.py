@@ -25,6 +25,7 @@ SYMBOLS = [
     "mp_verify_shuffle_batch_dev", "mp_verify_shuffle_chain", "mp_verify_shuffle_chain_dev", "mp_sync", "mp_reserve", "mp_set_latency_batch", "mp_remask_batch", "mp_msm", "mp_commit_batch",
     "mp_profile_enable", "mp_profile_report", "mp_work_census", "mp_plan_stats", "mp_sigma_prove_batch",
     "mp_sigma_verify_batch", "mp_blake2s", "mp_reveal_batch", "mp_unmask_batch", "mp_unmask_batch_dev",
+    "mp_mask_batch", "mp_verify_mask_batch", "mp_verify_mask_batch_dev", "mp_aggregate_keys_batch",
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
@@ -241,6 +242,10 @@ def bind(cdll):
     cdll.mp_reveal_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_unmask_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, c.c_size_t, u8p, u8p, u32p, i32p, i32p]
     cdll.mp_unmask_batch_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint32] + [c.c_void_p] * 3 + [c.c_size_t] + [c.c_void_p] * 5
+    cdll.mp_mask_batch.argtypes = [c.c_void_p, c.c_int, c.c_size_t, u8p, c.c_size_t, u32p, u8p, u8p, u8p, u8p, u8p, i32p]
+    cdll.mp_verify_mask_batch.argtypes = [c.c_void_p, c.c_int, c.c_size_t, u8p, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_verify_mask_batch_dev.argtypes = [c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
+    cdll.mp_aggregate_keys_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, u8p, i32p, i32p]
     for fn, at in (("mp_serialized_point_size", [c.c_int]), ("mp_serialized_deck_size", [c.c_int, c.c_size_t]),
                    ("mp_serialized_params_size", [c.c_int, c.c_uint32]), ("mp_serialized_proof_size", [c.c_int, c.c_uint32, c.c_uint32])):
         getattr(cdll, fn).argtypes = at
@@ -713,6 +718,53 @@ class Table:
         """the same with device pointers (d_cards may be the prover's d_out_decks); outputs are final after Engine.sync()"""
         self.eng._chk(self.lib.mp_unmask_batch_dev(self.h, K, d_keys, C, d_cards, T, d_signer, d_tokens, d_proofs, n_plain, d_plain_cards,
                                                    d_out_plain, d_out_index, d_token_status, d_card_status))
+
+    # ---- dealing and seating: K aggregate keys, C cards with a key index each; kind: DEAL_MASK (inputs = plaintext cards, one point
+    #      each) or DEAL_REMASK (inputs = masked cards)
+    DEAL_MASK, DEAL_REMASK = 0, 1
+
+    def _deal_shape(self, kind, keys, key_index, inputs):
+        K, C = len(keys) // self.pb, len(key_index)
+        self._need("keys", len(keys), K * self.pb)
+        self._need("inputs", len(inputs), C * (self.cb if kind == self.DEAL_REMASK else self.pb))
+        return K, C, (ctypes.c_uint32 * max(C, 1))(*key_index)
+
+    def mask_batch(self, kind, keys, key_index, inputs, factors, seeds):
+        """whoever deals: masked = in + (r G, r pk[key_index]) with its Chaum-Pedersen proof, per card -> (masked cards, proofs, status)"""
+        K, C, ki = self._deal_shape(kind, keys, key_index, inputs)
+        psz = 2 * self.pb + 32
+        self._need("masking factors", len(factors), C * 32)
+        self._need("prover seeds", len(seeds), C * 32)
+        out = (ctypes.c_uint8 * max(C * self.cb, 1))()
+        prf = (ctypes.c_uint8 * max(C * psz, 1))()
+        st = (ctypes.c_int32 * max(C, 1))()
+        self.eng._chk(self.lib.mp_mask_batch(self.h, kind, K, _in(keys), C, ki, _in(inputs), _in(factors), _in(seeds), out, prf, st))
+        return bytes(out)[:C * self.cb], bytes(prf)[:C * psz], list(st)[:C]
+
+    def verify_mask_batch(self, kind, keys, key_index, inputs, masked, proofs):
+        """every player: one status word per card (0, 6 "Chaum-Pedersen" or < 0)"""
+        K, C, ki = self._deal_shape(kind, keys, key_index, inputs)
+        self._need("masked cards", len(masked), C * self.cb)
+        self._need("proofs", len(proofs), C * (2 * self.pb + 32))
+        st = (ctypes.c_int32 * max(C, 1))()
+        self.eng._chk(self.lib.mp_verify_mask_batch(self.h, kind, K, _in(keys), C, ki, _in(inputs), _in(masked), _in(proofs), st))
+        return list(st)[:C]
+
+    def verify_mask_batch_dev(self, kind, K, d_keys, C, d_key_index, d_inputs, d_masked, d_proofs, d_status):
+        """the same with device pointers (d_inputs may be a prover's d_out_decks); d_status is final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_verify_mask_batch_dev(self.h, kind, K, d_keys, C, d_key_index, d_inputs, d_masked, d_proofs, d_status))
+
+    def aggregate_keys_batch(self, tables, P, keys, proofs, fs_init):
+        """seating: lane = table * P + seat -> (aggregate keys, player status, table status)"""
+        B = tables * P
+        self._need("keys", len(keys), B * self.pb)
+        self._need("proofs", len(proofs), B * (self.pb + 32))
+        self._need("fs_init", len(fs_init), B * 32)
+        out = (ctypes.c_uint8 * max(tables * self.pb, 1))()
+        ps = (ctypes.c_int32 * max(B, 1))()
+        ts = (ctypes.c_int32 * max(tables, 1))()
+        self.eng._chk(self.lib.mp_aggregate_keys_batch(self.h, tables, P, _in(keys), _in(proofs), _in(fs_init), out, ps, ts))
+        return bytes(out)[:tables * self.pb], list(ps)[:B], list(ts)[:tables]
 
     def set_io_chunk(self, proofs):
         """proofs per pipelined chunk of the host-buffer entry points (0 = default 65536)"""

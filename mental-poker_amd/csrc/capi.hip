@@ -1120,6 +1120,58 @@ int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, con
   MP_CATCH
 }
 
+// ---- dealing and seating: masking / remasking with their proofs, and the tables' aggregate keys (engine_core.hpp "dealing and seating")
+static const size_t DEAL_MAX_LANES = 1048576, DEAL_MAX_KEYS = 1048576;
+static bool deal_shape_ok(int kind, size_t K, size_t C) {
+  return (kind == MP_DEAL_MASK || kind == MP_DEAL_REMASK) && K >= 1 && K <= DEAL_MAX_KEYS && C >= 1 && C <= DEAL_MAX_LANES;
+}
+static const char* const DEAL_SHAPE = "kind is MP_DEAL_MASK or MP_DEAL_REMASK, 1 <= C <= 1 048 576, 1 <= K <= 1 048 576";
+int mp_mask_batch(mp_table* t, int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                  const uint8_t* factors, const uint8_t* prover_seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) {
+  if (!t || !keys || !key_index || !inputs || !factors || !prover_seeds || !out_masked || !out_proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_mask_batch: null argument");
+  if (!deal_shape_ok(kind, K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_mask_batch: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->mask_host(kind, K, keys, C, key_index, inputs, factors, prover_seeds, out_masked, out_proofs, status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_verify_mask_batch(mp_table* t, int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                         const uint8_t* masked, const uint8_t* proofs, int32_t* status) {
+  if (!t || !keys || !key_index || !inputs || !masked || !proofs || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_mask_batch: null argument");
+  if (!deal_shape_ok(kind, K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_verify_mask_batch: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->verify_mask_host(kind, K, keys, C, key_index, inputs, masked, proofs, status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_verify_mask_batch_dev(mp_table* t, int kind, size_t K, const void* d_keys, size_t C, const void* d_key_index, const void* d_inputs,
+                             const void* d_masked, const void* d_proofs, void* d_status) {
+  if (!t || !d_keys || !d_key_index || !d_inputs || !d_masked || !d_proofs || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_mask_batch_dev: null argument");
+  if (!deal_shape_ok(kind, K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_verify_mask_batch_dev: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->verify_mask_dev(kind, K, (const uint8_t*)d_keys, C, (const uint32_t*)d_key_index, (const uint8_t*)d_inputs, (const uint8_t*)d_masked,
+                     (const uint8_t*)d_proofs, (int32_t*)d_status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
+                            uint8_t* out_keys, int32_t* player_status, int32_t* table_status) {
+  if (!t || !keys || !proofs || !fs_init || !out_keys || !player_status || !table_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_aggregate_keys_batch: null argument");
+  if (P < 1 || tables < 1 || tables > DEAL_MAX_LANES || tables * (size_t)P > DEAL_MAX_LANES)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_aggregate_keys_batch: 1 <= P, 1 <= tables, tables * P <= 1 048 576");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->aggregate_keys_host(tables, P, keys, proofs, fs_init, out_keys, player_status, table_status);
+  return MP_OK;
+  MP_CATCH
+}
+
 int mp_plan_stats(mp_table* t, uint64_t out[16]) {
   if (!t || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_plan_stats: bad argument");
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);

@@ -267,6 +267,16 @@ struct mp_table {
   virtual int unmask_dev(size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
                          const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain,
                          uint32_t* out_index, int32_t* token_status, int32_t* card_status, bool plain_validated = false) = 0;
+  // dealing and seating (kernels_deal.hpp): K keys, C cards with a key index each, kind = MP_DEAL_MASK | MP_DEAL_REMASK; mask_host /
+  // verify_mask_host / aggregate_keys_host take host buffers, verify_mask_dev device pointers
+  virtual void mask_host(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                         const uint8_t* factors, const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) = 0;
+  virtual void verify_mask_host(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
+  virtual void verify_mask_dev(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                               const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
+  virtual void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
+                                   uint8_t* out_keys, int32_t* player_status, int32_t* table_status) = 0;
   virtual void census(uint64_t* pt, uint64_t* vt, uint64_t* po, uint64_t* vo) = 0;
   virtual void plan_stats(uint64_t out[16]) = 0;
 };

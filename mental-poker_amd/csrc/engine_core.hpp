@@ -6,6 +6,7 @@
 #include "kernels_decompress.hpp"
 #include "kernels_sigma.hpp"
 #include "kernels_open.hpp"
+#include "kernels_deal.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
 
@@ -2350,6 +2351,248 @@ struct Table : mp_table {
     rt::d2h(out_tokens, dtok.p, (size_t)B * G_::PB, s);
     rt::d2h(out_proofs, dpf.p, (size_t)B * psz, s);
     rt::d2h(status, w.status.p, (size_t)B * 4, s);
+    rt::stream_sync(s);
+  }
+
+  // ---------------------------------------------------------------- dealing and seating (kernels_deal.hpp)
+  // Masking / remasking with their Chaum-Pedersen proofs, their verification, and the key-ownership proofs of the seated players with
+  // the tables' aggregate keys: one lane per card, or per player.  As in the opening phase the statements are filled on the device
+  // (k_deal_stmt, k_seat_stmt), G is the table's fixed base, the commitments enter the checks as affine addends, and the prover builds
+  // the window table of pk once for x pk and r pk.  What differs: the verifier's publics masked - in are computed here, one complete
+  // mixed addition each and one batched inversion for all of them.  Static plans; the workspace stays with the table.
+  struct DealState {
+    bool ready = false;
+    Phase vph, pph1, pph2, sph;     // checks of the verifier | (x G, x pk) | the commitments (r G, r pk) | checks of the seating proofs
+    PhaseDev vdev, pdev1, pdev2, sdev;
+    uint32_t nJ = 0, nD = 0, nT = 0;
+    uint32_t fs_seed[2][8];         // Blake2s("Masking Proof"), Blake2s("Remasking Proof")  [REF mod.rs:80-81]
+    Workspace w;
+    DevBuf<uint8_t> fs;             // [lanes][32]
+    DevBuf<uint32_t> sumJ, sumP, scratch;      // seating: one entry per table
+  } deal;
+  static SigmaLay seat_lay() {      // one base; the check slot is the dealing lanes' first one
+    SigmaLay l = make_sigma_lay(1);
+    l.chk = make_deal_lay().s.chk;
+    return l;
+  }
+  void deal_prepare(uint32_t B) {
+    rt::Stream s = ctx->stream;
+    const DealLay d = make_deal_lay();
+    const SigmaLay& l = d.s;
+    if (!deal.ready) {
+      FixedBases fb{n};
+      const SigmaLay sl = seat_lay();
+      uint32_t np = l.chk + 2;
+      {
+        PhaseBuilder pb(deal.vph, np, FCHUNK, VCHUNK);      // z g_i - c a_i - A_i, i = 0, 1
+        pb.begin(l.chk);
+        pb.fixed(l.z, fb.G());
+        pb.var(l.negc, l.a);
+        pb.addend(l.A, true);
+        pb.end();
+        pb.begin(l.chk + 1);
+        pb.var(l.z, l.g + 1);
+        pb.var(l.negc, l.a + 1);
+        pb.addend(l.A + 1, true);
+        pb.end();
+      }
+      {
+        PhaseBuilder pb(deal.pph1, np, FCHUNK, VCHUNK);
+        pb.begin(l.a);
+        pb.fixed(l.x, fb.G());
+        pb.end();
+        pb.begin(l.a + 1);
+        pb.var(l.x, l.g + 1);
+        pb.end();
+        pb.normalize(l.a, 2);
+      }
+      {
+        PhaseBuilder pb(deal.pph2, np, FCHUNK, VCHUNK);
+        pb.begin(l.A);
+        pb.fixed(l.r, fb.G());
+        pb.end();
+        pb.begin(l.A + 1);
+        pb.var(l.r, l.g + 1);
+        pb.end();
+        pb.normalize(l.A, 2);
+      }
+      {
+        PhaseBuilder pb(deal.sph, np, FCHUNK, VCHUNK);      // z G - c pk - A
+        pb.begin(sl.chk);
+        pb.fixed(sl.z, fb.G());
+        pb.var(sl.negc, sl.a);
+        pb.addend(sl.A, true);
+        pb.end();
+      }
+      // x pk and r pk share the base: both phases know the window table of pk as table slot 0, and the first one builds it
+      if (deal.pph1.tables.size() != 1 || deal.pph2.tables.size() != 1 || deal.pph1.tables[0].s != l.g + 1 || deal.pph2.tables[0].s != l.g + 1 ||
+          deal.pph1.tables[0].b != 0 || deal.pph2.tables[0].b != 0)
+        throw std::logic_error("deal plan: the phases do not share the table of pk");
+      deal.pph2.tables.clear();
+      deal.nJ = np;
+      for (const Phase* ph : {&deal.vph, &deal.pph1, &deal.pph2, &deal.sph}) {
+        deal.nD = std::max(deal.nD, ph->n_dslots);
+        deal.nT = std::max(deal.nT, ph->n_tslots);
+      }
+      deal.vdev.upload(deal.vph, s);
+      deal.pdev1.upload(deal.pph1, s);
+      deal.pdev2.upload(deal.pph2, s);
+      deal.sdev.upload(deal.sph, s);
+      const char* names[2] = {"Masking Proof", "Remasking Proof"};
+      for (int k = 0; k < 2; ++k) {
+        Blake2sState st;
+        blake2s_init(st);
+        uint32_t mblk[16] = {0};
+        memcpy(mblk, names[k], strlen(names[k]));
+        blake2s_compress(st, mblk, (uint32_t)strlen(names[k]), true);
+        memcpy(deal.fs_seed[k], st.h, 32);
+      }
+      deal.ready = true;
+    }
+    deal.w.fw = G_::FW;
+    deal.w.ensure(B, 6, d.nP, deal.nJ, deal.nD, deal.nT, nwin, (6 * (G_::PB + 1) + 32) / 4 + 4, s);
+    deal.fs.alloc((size_t)deal.w.cap * 32, s, false);
+    rt::dzero(deal.w.status.p, (size_t)deal.w.Bpad * 4, s);
+  }
+  DealStmtArgs deal_stmt_args(int kind, size_t K, const uint8_t* keys, const uint32_t* key_index, const uint8_t* inputs) {
+    DealStmtArgs a{};
+    Workspace& w = deal.w;
+    a.P = w.P.p; a.J = w.J.p; a.S = w.S.p; a.status = w.status.p;
+    a.keys = keys; a.key_index = key_index; a.inputs = inputs;
+    a.fbpts = fbpts.p;
+    a.fs_init = deal.fs.p;
+    memcpy(a.fs_seed, deal.fs_seed[kind == MP_DEAL_REMASK ? 1 : 0], 32);
+    a.l = make_deal_lay();
+    a.Bpad = w.Bpad; a.K = (uint32_t)K; a.g_base = FixedBases{n}.G(); a.remask = kind == MP_DEAL_REMASK ? 1u : 0u;
+    return a;
+  }
+  // every pointer a device pointer; everything is enqueued on the context's stream
+  void verify_mask_dev(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs,
+                       const uint8_t* masked, const uint8_t* proofs, int32_t* status) override {
+    const uint32_t B = (uint32_t)C_;
+    deal_prepare(B);
+    Workspace& w = deal.w;
+    const DealLay d = make_deal_lay();
+    const SigmaLay& l = d.s;
+    DealStmtArgs sa = deal_stmt_args(kind, K, keys, key_index, inputs);
+    sa.masked = masked;
+    MP_RUN(k_deal_stmt, C, B, 4, sa);
+    // the publics a_i = masked_i - in_i become affine before the transcript absorbs them: one batched inversion for both slots
+    normalize_flat(w.J.p + j_off<C>(l.a, w.Bpad, 0), w.P.p + p_off<C>(l.a, w.Bpad, 0), w.NS.p, (size_t)2 * w.Bpad);
+    SigmaIoArgs io{const_cast<uint8_t*>(proofs), w.S.p, w.P.p, w.status.p, l, w.Bpad};
+    MP_RUN(k_sigma_load, C, B, 3, io);
+    check_subgroup(w, B, l.g + 1, 1);      // the key (G is the table's own; the differences of subgroup points are subgroup points)
+    check_subgroup(w, B, l.A, 6);          // commitments, input card and masked card are consecutive P slots
+    const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+    SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 0};
+    MP_RUN(k_sigma_fs, C, B, 1, fa);
+    run_phase(deal.vdev, w, B);
+    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
+    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    DealFinishArgs fin{w.status.p, key_index, status, nullptr, nullptr, (uint32_t)K};
+    MP_RUN(k_deal_finish, C, B, 1, fin);
+  }
+  static size_t deal_input_bytes(int kind) { return (kind == MP_DEAL_REMASK ? 2 : 1) * (size_t)G_::PB; }
+  void verify_mask_host(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs,
+                        const uint8_t* masked, const uint8_t* proofs, int32_t* status) override {
+    rt::Stream s = ctx->stream;
+    const size_t psz = 2 * (size_t)G_::PB + 32, isz = deal_input_bytes(kind);
+    DevBuf<uint8_t> dk, din, dm, dp;
+    DevBuf<uint32_t> dki;
+    DevBuf<int32_t> dst;
+    dk.alloc(K * G_::PB, s, false); din.alloc(C_ * isz, s, false); dm.alloc(C_ * 2 * G_::PB, s, false); dp.alloc(C_ * psz, s, false);
+    dki.alloc(C_, s, false); dst.alloc(C_, s, false);
+    rt::h2d(dk.p, keys, K * G_::PB, s);
+    rt::h2d(din.p, inputs, C_ * isz, s);
+    rt::h2d(dm.p, masked, C_ * 2 * G_::PB, s);
+    rt::h2d(dp.p, proofs, C_ * psz, s);
+    rt::h2d(dki.p, key_index, C_ * 4, s);
+    verify_mask_dev(kind, K, dk.p, C_, dki.p, din.p, dm.p, dp.p, dst.p);
+    rt::d2h(status, dst.p, C_ * 4, s);
+    rt::stream_sync(s);
+  }
+  // (x G, x pk) first: the hedged nonce hashes the whole statement, the publics included (k_sigma_init)
+  void mask_host(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs, const uint8_t* factors,
+                 const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) override {
+    rt::Stream s = ctx->stream;
+    const uint32_t B = (uint32_t)C_;
+    const size_t psz = 2 * (size_t)G_::PB + 32, isz = deal_input_bytes(kind);
+    deal_prepare(B);
+    Workspace& w = deal.w;
+    const DealLay d = make_deal_lay();
+    const SigmaLay& l = d.s;
+    DevBuf<uint8_t> dk, din, dx, dseed, dm, dpf;
+    DevBuf<uint32_t> dki;
+    DevBuf<int32_t> dst;
+    dk.alloc(K * G_::PB, s, false); din.alloc(C_ * isz, s, false); dx.alloc(C_ * 32, s, false); dseed.alloc(C_ * 32, s, false);
+    dm.alloc(C_ * 2 * G_::PB, s, false); dpf.alloc(C_ * psz, s, false); dki.alloc(C_, s, false); dst.alloc(C_, s, false);
+    rt::h2d(dk.p, keys, K * G_::PB, s);
+    rt::h2d(din.p, inputs, C_ * isz, s);
+    rt::h2d(dx.p, factors, C_ * 32, s);
+    rt::h2d(dseed.p, seeds, C_ * 32, s);
+    rt::h2d(dki.p, key_index, C_ * 4, s);
+    DealStmtArgs sa = deal_stmt_args(kind, K, dk.p, dki.p, din.p);
+    sa.factors = dx.p;
+    MP_RUN(k_deal_stmt, C, B, 4, sa);
+    check_subgroup(w, B, l.g + 1, 1);      // the key and the input card, as the sigma calls test bases and publics
+    check_subgroup(w, B, d.in, 2);
+    run_phase(deal.pdev1, w, B);
+    DealAddArgs aa{w.P.p, w.J.p, d, w.Bpad};
+    MP_RUN(k_deal_add, C, B, 2, aa);
+    normalize_flat(w.J.p + j_off<C>(d.out, w.Bpad, 0), w.P.p + p_off<C>(d.out, w.Bpad, 0), w.NS.p, (size_t)2 * w.Bpad);
+    const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+    SigmaInitArgs ia{w.S.p, dseed.p, l, w.Bpad, f, w.P.p, deal.fs.p};
+    MP_RUN(k_sigma_init, C, B, 1, ia);
+    run_phase(deal.pdev2, w, B);             // (its table list is empty: the table of pk is the first phase's)
+    SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 1};
+    MP_RUN(k_sigma_fs, C, B, 1, fa);
+    SigmaIoArgs io{dpf.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
+    MP_RUN(k_sigma_store, C, B, 3, io);
+    StorePointsArgs so{dm.p, w.P.p, w.Bpad, 2, d.out};
+    MP_RUN(k_store_points, C, B, 2, so);
+    DealFinishArgs fin{w.status.p, dki.p, dst.p, dm.p, dpf.p, (uint32_t)K};
+    MP_RUN(k_deal_finish, C, B, 1, fin);
+    rt::d2h(out_masked, dm.p, C_ * 2 * G_::PB, s);
+    rt::d2h(out_proofs, dpf.p, C_ * psz, s);
+    rt::d2h(status, dst.p, C_ * 4, s);
+    rt::stream_sync(s);
+  }
+  // seating: lane = table * seats + seat
+  void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init, uint8_t* out_keys,
+                           int32_t* player_status, int32_t* table_status) override {
+    rt::Stream s = ctx->stream;
+    const uint32_t Tn = (uint32_t)tables, B = Tn * seats;
+    const size_t psz = (size_t)G_::PB + 32;
+    deal_prepare(B);
+    Workspace& w = deal.w;
+    const SigmaLay l = seat_lay();
+    DevBuf<uint8_t> dk, dp, dout;
+    DevBuf<int32_t> dps, dts;
+    dk.alloc((size_t)B * G_::PB, s, false); dp.alloc((size_t)B * psz, s, false); dout.alloc((size_t)Tn * G_::PB, s, false);
+    dps.alloc(B, s, false); dts.alloc(Tn, s, false);
+    deal.sumJ.alloc((size_t)Tn * G_::JW, s, false); deal.sumP.alloc((size_t)Tn * G_::PW, s, false); deal.scratch.alloc((size_t)Tn * G_::FW, s, false);
+    rt::h2d(dk.p, keys, (size_t)B * G_::PB, s);
+    rt::h2d(dp.p, proofs, (size_t)B * psz, s);
+    rt::h2d(deal.fs.p, fs_init, (size_t)B * 32, s);
+    SeatStmtArgs sa{w.P.p, w.status.p, dk.p, fbpts.p, l, w.Bpad, FixedBases{n}.G()};
+    MP_RUN(k_seat_stmt, C, B, 2, sa);
+    SigmaIoArgs io{dp.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
+    MP_RUN(k_sigma_load, C, B, 2, io);
+    check_subgroup(w, B, l.a, 2);          // key and commitment are consecutive P slots
+    const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+    SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 0};
+    MP_RUN(k_sigma_fs, C, B, 1, fa);
+    run_phase(deal.sdev, w, B);
+    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 5};
+    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    KeySumArgs ka{w.P.p, w.status.p, deal.sumJ.p, dps.p, dts.p, w.Bpad, seats, l.a};
+    MP_RUN(k_key_sum, C, Tn, 1, ka);
+    normalize_flat(deal.sumJ.p, deal.sumP.p, deal.scratch.p, Tn);
+    StorePointsArgs so{dout.p, deal.sumP.p, Tn, 1, 0};      // (the identity is zero bytes on the wire: a refused table's key)
+    MP_RUN(k_store_points, C, Tn, 1, so);
+    rt::d2h(out_keys, dout.p, (size_t)Tn * G_::PB, s);
+    rt::d2h(player_status, dps.p, (size_t)B * 4, s);
+    rt::d2h(table_status, dts.p, (size_t)Tn * 4, s);
     rt::stream_sync(s);
   }
 

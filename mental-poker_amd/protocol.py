@@ -391,6 +391,84 @@ class DLCards:
                 out.append((plain[i * pb:(i + 1) * pb], idx[i] if idx[i] != _native.Table.NO_INDEX else None))
         return out
 
+    # -- dealing and seating in batches: mask / verify_mask / remask / verify_remask for the cards of many tables, and
+    #    compute_aggregate_key for many tables, in one call each (mp_mask_batch, mp_verify_mask_batch, mp_aggregate_keys_batch; the
+    #    statements are assembled on the device)                                                    [REF examples/round.rs:228-262]
+    def _deal_shape(self, shared_keys, key_index, inputs, input_bytes):
+        pb = self.engine.point_bytes
+        if not shared_keys or not inputs or len(key_index) != len(inputs):
+            raise CardProtocolError.io("at least one key and one card, and one key index per card")
+        if any(len(bytes(k)) != pb for k in shared_keys) or any(len(bytes(c)) != input_bytes for c in inputs):
+            raise CardProtocolError.io("a key is %d bytes, an input card %d" % (pb, input_bytes))
+        if any(not 0 <= int(k) < 1 << 32 for k in key_index):
+            raise CardProtocolError.io("a key index is an index into the keys")
+
+    def _deal(self, kind, rng_seeds, pp, shared_keys, key_index, inputs, factors):
+        pb = self.engine.point_bytes
+        self._deal_shape(shared_keys, key_index, inputs, 2 * pb if kind == _native.Table.DEAL_REMASK else pb)
+        if len(rng_seeds) != len(inputs) or len(factors) != len(inputs) or any(len(bytes(s)) != 32 for s in rng_seeds):
+            raise CardProtocolError.io("one 32-byte prover seed and one masking factor per card")
+        try:
+            out, prf, st = self._t(pp).mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index],
+                                                  b"".join(bytes(c) for c in inputs),
+                                                  _scalar_bytes([f % CURVE_ORDERS[self.curve] for f in factors]), b"".join(bytes(s) for s in rng_seeds))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        cb, psz = 2 * pb, 2 * pb + 32
+        return [(out[i * cb:(i + 1) * cb], prf[i * psz:(i + 1) * psz]) if v == 0 else CardProtocolError.io(self.engine.check_name(v))
+                for i, v in enumerate(st)]
+
+    def _verify_deal(self, kind, pp, shared_keys, key_index, inputs, masked_cards, proofs):
+        pb = self.engine.point_bytes
+        self._deal_shape(shared_keys, key_index, inputs, 2 * pb if kind == _native.Table.DEAL_REMASK else pb)
+        if len(masked_cards) != len(inputs) or len(proofs) != len(inputs) or any(len(bytes(c)) != 2 * pb for c in masked_cards) or \
+                any(len(bytes(p)) != 2 * pb + 32 for p in proofs):
+            raise CardProtocolError.io("one %d-byte masked card and one %d-byte proof per card" % (2 * pb, 2 * pb + 32))
+        try:
+            st = self._t(pp).verify_mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index],
+                                               b"".join(bytes(c) for c in inputs), b"".join(bytes(c) for c in masked_cards),
+                                               b"".join(bytes(p) for p in proofs))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        return [None if v == 0 else CryptoError(self.engine.check_name(v)) if v > 0 else CardProtocolError.io(self.engine.check_name(v)) for v in st]
+
+    def deal(self, rng_seeds, pp, shared_keys, key_index, cards, factors):
+        """`mask` for many cards: card i (a plaintext card) is masked under shared_keys[key_index[i]] with the factor factors[i];
+        rng_seeds: one fresh 32-byte seed per card -> per card (MaskedCard, ZKProofMasking), or the CardProtocolError of its lane"""
+        return self._deal(_native.Table.DEAL_MASK, rng_seeds, pp, shared_keys, key_index, cards, factors)
+
+    def verify_deal(self, pp, shared_keys, key_index, cards, masked_cards, proofs):
+        """`verify_mask` for many cards -> per card None, or the error `verify_mask` raises for it: CryptoError("Chaum-Pedersen") /
+        CardProtocolError.io(...)"""
+        return self._verify_deal(_native.Table.DEAL_MASK, pp, shared_keys, key_index, cards, masked_cards, proofs)
+
+    def deal_remask(self, rng_seeds, pp, shared_keys, key_index, masked_cards, factors):
+        """`remask` for many cards -> per card (MaskedCard, ZKProofRemasking), or the CardProtocolError of its lane"""
+        return self._deal(_native.Table.DEAL_REMASK, rng_seeds, pp, shared_keys, key_index, masked_cards, factors)
+
+    def verify_deal_remask(self, pp, shared_keys, key_index, original_cards, remasked_cards, proofs):
+        """`verify_remask` for many cards -> per card None, or the error `verify_remask` raises for it"""
+        return self._verify_deal(_native.Table.DEAL_REMASK, pp, shared_keys, key_index, original_cards, remasked_cards, proofs)
+
+    def compute_aggregate_keys(self, pp, tables):
+        """`compute_aggregate_key` for many tables: tables = [[(pk, proof, player_public_info)]], the same number of players at each
+        -> per table the AggregatePublicKey, or the error `compute_aggregate_key` raises for it:
+        CardProtocolError("ProofVerificationError", CryptoError("Schnorr Identification")) / CardProtocolError.io(...)"""
+        pb = self.engine.point_bytes
+        if not tables or not tables[0] or any(len(t) != len(tables[0]) for t in tables):
+            raise CardProtocolError.io("at least one table, and the same number of players (at least one) at each")
+        rows = [row for t in tables for row in t]
+        if any(len(bytes(pk)) != pb or len(bytes(proof)) != pb + 32 for pk, proof, _ in rows):
+            raise CardProtocolError.io("a key is %d bytes, a proof of key ownership %d" % (pb, pb + 32))
+        try:
+            keys, _, ts = self._t(pp).aggregate_keys_batch(len(tables), len(tables[0]), b"".join(bytes(pk) for pk, _, _ in rows),
+                                                           b"".join(bytes(proof) for _, proof, _ in rows),
+                                                           b"".join(self.engine.blake2s(KEY_OWN_RNG_SEED + bytes(info)) for _, _, info in rows))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        return [keys[k * pb:(k + 1) * pb] if v == 0 else CardProtocolError("ProofVerificationError", CryptoError(self.engine.check_name(v))) if v > 0
+                else CardProtocolError.io(self.engine.check_name(v)) for k, v in enumerate(ts)]
+
     # -- batched forms (the data-parallel axis: independent proofs of one table)
     def shuffle_and_remask_batch(self, rng_seeds, pp, shared_key, decks, masking_factors, permutations):
         t = self.table(pp, shared_key)
