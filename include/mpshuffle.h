@@ -463,6 +463,34 @@ int mp_verify_mask_batch_dev(mp_table* t, int kind, size_t K, const void* d_keys
 int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                             uint8_t* out_keys, int32_t* player_status, int32_t* table_status);
 
+/* ---- screening the sigma verifiers with grouped bucket equations (opt-in, off by default) -------------------------------------------
+ * mp_unmask_batch[_dev], mp_verify_mask_batch[_dev], mp_aggregate_keys_batch and mp_sigma_verify_batch check every proof on a plan of its
+ * own: per lane about 3 x (51 + 15) additions and 500 doublings.  With the screen on, the checks z g_i - c a_i - A_i = O of a GROUP of
+ * consecutive lanes are added up -- each check with a weight of its own, two per Chaum-Pedersen lane, one per Schnorr lane -- into ONE
+ * multi-scalar multiplication on the bucket pipeline of the shuffle verifier (a lane is five points of it where one base is the table's
+ * G, about 18-33 additions each; G itself is one fixed-base term per group).  The weights are Fr::rand of ChaCha20(Blake2s(...)) over a
+ * digest of every lane of the group -- bases, publics, commitments AND the response z, which the proof's own transcript never absorbs --,
+ * so an error in one lane cannot cancel against another's except with probability ~2^-250; no host randomness is involved.  A group
+ * whose equation fails, or that holds a lane already refused (encoding, subgroup, argument), is re-verified lane by lane on the per-proof
+ * path -- its lanes only --, so every status word and every output byte is what the unscreened call gives; no honest lane is refused by
+ * the screen alone.  Subgroup and curve tests stay per point, before the screen.
+ *   lanes_per_group   0 = off (the default); MP_SIGMA_SCREEN_AUTO = sized by points like the groups of mp_set_group_verify (equations
+ *                     for the split pipeline when the call brings enough points, honouring mp_set_bucket_bits / mp_set_bucket_split;
+ *                     64 equations for the one-wave-per-window kernel below that; calls too small for groups of 16 lanes stay per
+ *                     proof); any other value = lanes per group (the last group of a call may be short).  A value whose equation
+ *                     cannot fit one bucket job (6 x lanes > 589 824 points) is MP_ERR_BAD_ARGUMENT.
+ *   min_lanes         calls with fewer lanes keep the per-proof path.
+ * On a curve with a cofactor (MP_CURVE_BLS12_377) the screen runs only while mp_set_subgroup_check is on: without the per-point test a
+ * weighted sum and a per-proof check can disagree on points with a low-order component; with the test off every call takes the
+ * per-proof path.
+ * The _dev forms: with the screen on, a screened call WAITS ONCE for a 4-byte flag (as mp_verify_shuffle_batch_dev does under merged
+ * verification), and once more for one word per group if some group failed; with the screen off they never wait.
+ * mp_sigma_screen_stats: counters since the last mp_set_sigma_screen -- [0] lanes that went through a screening equation, [1] group
+ * equations evaluated, [2] groups that failed, [3] lanes re-verified on the per-proof path.  Both calls hold the context's lock. */
+#define MP_SIGMA_SCREEN_AUTO 0xFFFFFFFFu
+int mp_set_sigma_screen(mp_table* t, uint32_t lanes_per_group, size_t min_lanes);
+int mp_sigma_screen_stats(const mp_table* t, uint64_t out[4]);
+
 /* ---- canonical serialisation (arkworks-0.3 `CanonicalSerialize` / `CanonicalDeserialize`, compressed) ----------------------
  * Every associated type of the trait is CanonicalSerialize + CanonicalDeserialize [REF src/lib.rs:45-71], and the reference's
  * harness measures `proof.serialized_size()` [REF examples/parameter_selection.rs:95]: these are the conversions between those

@@ -26,6 +26,7 @@ SYMBOLS = [
     "mp_profile_enable", "mp_profile_report", "mp_work_census", "mp_plan_stats", "mp_sigma_prove_batch",
     "mp_sigma_verify_batch", "mp_blake2s", "mp_reveal_batch", "mp_unmask_batch", "mp_unmask_batch_dev",
     "mp_mask_batch", "mp_verify_mask_batch", "mp_verify_mask_batch_dev", "mp_aggregate_keys_batch",
+    "mp_set_sigma_screen", "mp_sigma_screen_stats",
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
@@ -246,6 +247,8 @@ def bind(cdll):
     cdll.mp_verify_mask_batch.argtypes = [c.c_void_p, c.c_int, c.c_size_t, u8p, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_verify_mask_batch_dev.argtypes = [c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
     cdll.mp_aggregate_keys_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, u8p, i32p, i32p]
+    cdll.mp_set_sigma_screen.argtypes = [c.c_void_p, c.c_uint32, c.c_size_t]
+    cdll.mp_sigma_screen_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
     for fn, at in (("mp_serialized_point_size", [c.c_int]), ("mp_serialized_deck_size", [c.c_int, c.c_size_t]),
                    ("mp_serialized_params_size", [c.c_int, c.c_uint32]), ("mp_serialized_proof_size", [c.c_int, c.c_uint32, c.c_uint32])):
         getattr(cdll, fn).argtypes = at
@@ -870,6 +873,21 @@ class Table:
     def set_toom_cook(self, on=True):
         """3 <= m <= 8: Toom-Cook (default) or Karatsuba evaluation of the multi-exponentiation diagonals"""
         self.eng._chk(self.lib.mp_set_toom_cook(self.h, 1 if on else 0))
+
+    SIGMA_SCREEN_AUTO = 0xFFFFFFFF      # MP_SIGMA_SCREEN_AUTO
+
+    def set_sigma_screen(self, lanes_per_group=SIGMA_SCREEN_AUTO, min_lanes=1024):
+        """screening of the sigma verifiers (unmask_batch[_dev], verify_mask_batch[_dev], aggregate_keys_batch, sigma_verify_batch): the
+        checks of `lanes_per_group` consecutive lanes as one weighted equation on the bucket kernels, the lanes of a failing group re-verified
+        one by one -- same status words, same outputs.  0 = off (the default), SIGMA_SCREEN_AUTO = sized by points; calls with fewer than
+        min_lanes lanes keep the per-proof path.  With it on, the *_dev forms wait once for a 4-byte flag.  Resets sigma_screen_stats."""
+        self.eng._chk(self.lib.mp_set_sigma_screen(self.h, lanes_per_group, min_lanes))
+
+    def sigma_screen_stats(self):
+        """since the last set_sigma_screen: [lanes screened, group equations evaluated, groups that failed, lanes re-verified per proof]"""
+        v = (ctypes.c_uint64 * 4)()
+        self.eng._chk(self.lib.mp_sigma_screen_stats(self.h, v))
+        return [int(x) for x in v]
 
     def set_subgroup_check(self, on=True):
         """curves with a cofactor: test every wire point for membership in the prime-order subgroup (default on)"""

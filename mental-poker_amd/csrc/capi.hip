@@ -478,6 +478,21 @@ int mp_set_toom_cook(mp_table* t, int on) {
   return MP_OK;
   MP_CATCH
 }
+int mp_set_sigma_screen(mp_table* t, uint32_t lanes_per_group, size_t min_lanes) {
+  if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_sigma_screen: null table");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  if (t->set_sigma_screen(lanes_per_group, min_lanes) != MP_OK)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_set_sigma_screen: 0 (off), MP_SIGMA_SCREEN_AUTO or up to 98 304 lanes per group (one bucket job)");
+  return MP_OK;
+  MP_CATCH
+}
+int mp_sigma_screen_stats(const mp_table* t, uint64_t out[4]) {
+  if (!t || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_sigma_screen_stats: null argument");
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (a verify call on another thread writes the counters)
+  t->sigma_screen_stats(out);
+  return MP_OK;
+}
 int mp_set_subgroup_check(mp_table* t, int on) {
   if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_subgroup_check: null table");
   std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);

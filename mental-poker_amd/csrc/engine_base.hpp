@@ -277,6 +277,9 @@ struct mp_table {
                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
   virtual void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                                    uint8_t* out_keys, int32_t* player_status, int32_t* table_status) = 0;
+  // screening of the sigma verifiers (kernels_screen.hpp; mp_set_sigma_screen): lanes per group equation (0 = off), the smallest call screened
+  virtual int set_sigma_screen(uint32_t lanes_per_group, size_t min_lanes) = 0;
+  virtual void sigma_screen_stats(uint64_t out[4]) const = 0;
   virtual void census(uint64_t* pt, uint64_t* vt, uint64_t* po, uint64_t* vo) = 0;
   virtual void plan_stats(uint64_t out[16]) = 0;
 };

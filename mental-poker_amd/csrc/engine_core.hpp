@@ -7,6 +7,7 @@
 #include "kernels_sigma.hpp"
 #include "kernels_open.hpp"
 #include "kernels_deal.hpp"
+#include "kernels_screen.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
 
@@ -1709,6 +1710,20 @@ struct Table : mp_table {
   // contiguous run per equation (tile(run): k_chain_tile / k_group_tile; tiled = false: the bucket kernel takes them from their P slots),
   // ONE bucket MSM + fixed-base part per equation, the verdicts: flag, gbad[t], and in e.status 0 for every link of an equation that holds
   // (final), MP_ERR_INTERNAL for those of the others until the finer passes have given each its own word
+  // the value of T equations into J slot 0 of the lanes 0 .. T - 1 of w: scalars cs [terms][Tpad], ONE bucket MSM + fixed-base part each
+  // (shared by the equations of chains and groups and by those of the sigma screen)
+  void run_equation_msm(Workspace& w, PhaseDev& ph, const uint32_t* cs, int16_t* d8, uint32_t T, const char* too_many, const uint32_t* run, uint32_t K) {
+    const uint32_t Tpad = (T + 63u) & ~63u;
+    run_bucket(w, ph, cs, Tpad, d8, (size_t)ph.b_dig_bytes, T, T, too_many, run, K);
+    FixedArgs fx{cs, w.J.p, FB.p, ph.fjobs.p, ph.fterms.p, w.Bpad, fbg, Tpad};
+    MP_RUN(k_fixed_msm, C, T, ph.n_f, fx);
+    if (ph.n_c0) {
+      CombineArgs cb0{w.J.p, w.P.p, ph.cjobs0.p, ph.cterms0.p, w.Bpad};
+      MP_RUN(k_combine, C, T, ph.n_c0, cb0);
+    }
+    CombineArgs cb{w.J.p, w.P.p, ph.cjobs.p, ph.cterms.p, w.Bpad};
+    MP_RUN(k_combine, C, T, ph.n_c, cb);
+  }
   template <class Tile>
   void run_equations(Workspace& w, ChainPlan& p, const EquationArgs& e, bool tiled, Tile tile) {
     const uint32_t T = e.T, Tpad = (T + 63u) & ~63u, nterms = p.K + p.nfix;
@@ -1723,15 +1738,7 @@ struct Table : mp_table {
       tile(gt.p);
       run = gt.p;
     }
-    run_bucket(w, ph, chain_cs.p, Tpad, chain_d8.p, (size_t)ph.b_dig_bytes, T, T, e.too_many, run, p.K);
-    FixedArgs fx{chain_cs.p, w.J.p, FB.p, ph.fjobs.p, ph.fterms.p, w.Bpad, fbg, Tpad};
-    MP_RUN(k_fixed_msm, C, T, ph.n_f, fx);
-    if (ph.n_c0) {
-      CombineArgs cb0{w.J.p, w.P.p, ph.cjobs0.p, ph.cterms0.p, w.Bpad};
-      MP_RUN(k_combine, C, T, ph.n_c0, cb0);
-    }
-    CombineArgs cb{w.J.p, w.P.p, ph.cjobs.p, ph.cterms.p, w.Bpad};
-    MP_RUN(k_combine, C, T, ph.n_c, cb);
+    run_equation_msm(w, ph, chain_cs.p, chain_d8.p, T, e.too_many, run, p.K);
     uint32_t* gb = e.gbad;
     if (!gb) {
       gbad[e.vlane ? 1 : 0].alloc(T, s, false);
@@ -2065,6 +2072,193 @@ struct Table : mp_table {
     out[14] = N | ((uint64_t)(ps[0].pplan.toom.E ? m : 0u) << 32);      // high word: m if k_toom_points runs in this plan
     out[15] = bucket_terms | (bucket_jobs << 32);      // variable-base terms / MSMs on the bucket kernel (prove + verify)
   }
+  // ---------------------------------------------------------------- sigma screening (kernels_screen.hpp; mp_set_sigma_screen)
+  // Opt-in: the Chaum-Pedersen / Schnorr verifiers behind opening, dealing and seating check every proof on a Straus plan of its own
+  // (~3 x (51 + 15) additions and ~500 doublings a lane).  With the screen on, the checks z g_i - c a_i - A_i = O of g consecutive lanes
+  // are added up, each with a weight of its own, into ONE equation: 3 nb points a lane (one fewer where a base is the table's G, which
+  // collapses into one fixed-base term per 64 lanes), ~18-33 additions a point on the bucket pipeline.  A group whose equation fails, or
+  // that holds a lane whose status word is set already, goes through the verifier's own per-proof phase -- its lanes only --, so every
+  // status word is the one the unscreened call gives.  Weights: Fr::rand of ChaCha20(Blake2s(...)) over the lane digests of the whole
+  // group (k_screen_digest: transcript state AND response), through k_chain_digest / k_chain_weights.
+  struct SigmaScreen {
+    uint32_t lanes = 0;               // 0 = off, MP_SIGMA_SCREEN_AUTO = by points, else lanes per group
+    uint32_t min_lanes = 0;
+    uint64_t stats[4] = {0, 0, 0, 0};
+    // the plan of one group equation, cached by (nbases, which base is G, lanes per group, window width)
+    uint32_t nb = 0, g = 0, bits = 0, per = 0;
+    int gi = -2;
+    ChainPlan plan;
+    std::vector<ScreenTerm> terms;
+    DevBuf<ScreenTerm> dterms;
+    uint32_t pslot[8];
+    Workspace w;                      // lean: the equations' J slots and the bucket kernels' scratch
+    Workspace rw;                     // the lanes of failing groups, compacted: what the verifier's phase needs
+    DevBuf<uint32_t> seeds, dig, cw, cs, tile, part, gbad, flag, idx;
+    DevBuf<int16_t> d16;
+  } scr;
+  static const uint32_t SCREEN_POINTS_PER_LANE_MAX = 6;      // Chaum-Pedersen, neither base the table's G
+  int set_sigma_screen(uint32_t lanes, size_t min_lanes) override {
+    if (lanes != MP_SIGMA_SCREEN_AUTO && (uint64_t)lanes * SCREEN_POINTS_PER_LANE_MAX > BUCKET_TERMS_MAX) return MP_ERR_BAD_ARGUMENT;
+    scr.lanes = lanes;
+    scr.min_lanes = (uint32_t)std::min<size_t>(min_lanes, 0xFFFFFFFFu);
+    for (uint64_t& v : scr.stats) v = 0;
+    return MP_OK;
+  }
+  void sigma_screen_stats(uint64_t out[4]) const override {
+    for (int i = 0; i < 4; ++i) out[i] = scr.stats[i];
+  }
+  // Lanes per group for a call of B lanes of `per` points; 0 = this call keeps the per-proof path.  An explicit size is taken as it is.
+  // AUTO sizes by points like group_size (mp_set_group_verify, mp_set_bucket_bits / _split decide the kernel from there): a call with
+  // enough points for the split pipeline (GROUP_WG_POINTS_MIN) takes equations of up to group_points_wg points, as few and as even as
+  // B allows -- its units are a thirty-second of a window, one equation already spreads over the chip.  Below that the
+  // one-wave-per-window kernel wants an (equation, window) item per persistent wave: 64 equations of 32 windows, up to group_points
+  // points each; groups of fewer than 16 lanes pay a window's reduction (~40 additions) for ~80 points and stay on the Straus plans.
+  uint32_t screen_group_lanes(uint32_t B, uint32_t per) const {
+    if (scr.lanes != MP_SIGMA_SCREEN_AUTO) return std::min(scr.lanes, B);
+    uint32_t want = 0;
+    if (group_points_wg && (uint64_t)B * per >= GROUP_WG_POINTS_MIN) {
+      want = std::min<uint32_t>((group_points_wg + per / 2) / per, B);
+    } else if (group_points) {
+      want = std::min<uint32_t>((group_points + per / 2) / per, B / 64u);
+      if (want < 16) return 0;
+    }
+    if (want < 2) return 0;
+    const uint32_t T = (B + want - 1) / want;
+    return (B + T - 1) / T;
+  }
+  // The plan builder: the variable terms of a lane over SigmaLay -- (z, g_i) unless g_i is the table's G, (-c, a_i), (-1, A_i) with
+  // the weight of check i -- in the order k_screen_tile lays the lane's points out; G's terms collapsed as build_equation_plan
+  // collapses the fixed bases (runs of at most 64 lanes)
+  void build_screen_plan(const SigmaLay& l, int gi, uint32_t g, uint32_t bits) {
+    if (scr.nb == l.nb && scr.gi == gi && scr.g == g && scr.bits == bits) return;
+    if (scr.g) rt::stream_sync(ctx->stream);      // (the plan being replaced may still be read)
+    ChainPlan& p = scr.plan;
+    p.ph = Phase();
+    scr.terms.clear();
+    uint32_t next_partial = 1;                    // J slot 0 = the equation's value
+    PhaseBuilder pb(p.ph, next_partial, FCHUNK, VCHUNK, 1u, bk_windows(R::BITS, bits), 1u, bits);
+    pb.begin(0);
+    uint32_t per = 0;
+    for (uint32_t i = 0; i < l.nb; ++i) {
+      if ((int)i != gi) scr.pslot[per++] = l.g + i;
+      scr.pslot[per++] = l.a + i;
+      scr.pslot[per++] = l.A + i;
+    }
+    auto var = [&](uint32_t s, uint32_t pslot, uint32_t j, uint32_t i) {
+      pb.var((uint32_t)scr.terms.size(), (uint32_t)scr.terms.size());      // (a term's point: its index in the group's contiguous run)
+      scr.terms.push_back(ScreenTerm{s, pslot, j, 1u, i});
+    };
+    for (uint32_t j = 0; j < g; ++j)
+      for (uint32_t i = 0; i < l.nb; ++i) {
+        if ((int)i != gi) var(l.z, l.g + i, j, i);
+        var(l.negc, l.a + i, j, i);
+        var(l.minus_one, l.A + i, j, i);
+      }
+    p.K = (uint32_t)scr.terms.size();
+    if (gi >= 0)
+      for (uint32_t j0 = 0; j0 < g; j0 += 64u) {
+        pb.fixed((uint32_t)scr.terms.size(), FixedBases{n}.G());
+        scr.terms.push_back(ScreenTerm{l.z, NO_SLOT, j0, std::min(64u, g - j0), (uint32_t)gi});
+      }
+    p.nfix = (uint32_t)scr.terms.size() - p.K;
+    pb.end();
+    p.nJ = next_partial;
+    p.dev.upload(p.ph, ctx->stream);
+    scr.dterms.upload(scr.terms, ctx->stream);
+    scr.nb = l.nb; scr.gi = gi; scr.g = g; scr.bits = bits; scr.per = per;
+  }
+  // what a verifier hands over in place of "run_phase(vdev); k_sigma_verdict": its lanes in w (statement, commitments, z, -c, -1 and the
+  // transcript state in place, subgroup and encoding findings in w.status), gi = which base is the table's G (-1: none), its per-proof
+  // phase and what that needs of a workspace.  true: w.status holds the final word of every lane; false: not screened, the caller goes on
+  // as before.  Waits once for the 4-byte flag; a second time, for the groups' words, only if some group failed.
+  struct ScreenCall {
+    const SigmaLay& l;
+    int gi;
+    PhaseDev& vdev;
+    uint32_t nP, nJ, nD, nT;
+    int32_t fail_code;
+  };
+  bool screen_sigma(Workspace& w, uint32_t B, const ScreenCall& c) {
+    if (!scr.lanes || !B || B < scr.min_lanes || B > 0x7FFFFFFFu || c.l.nb > 2) return false;
+    // (a curve with a cofactor: without the per-point subgroup test a weighted sum and a per-proof check can disagree on points with a
+    // low-order component -- the screen runs only while the test does)
+    if (!Cofactor<C>::ONE && !subgroup_check) return false;
+    const SigmaLay& l = c.l;
+    const uint32_t per = 3 * l.nb - (c.gi >= 0 ? 1u : 0u);
+    const uint32_t g = screen_group_lanes(B, per);
+    if (!g) return false;
+    const uint32_t K = g * per, bits = bucket_bits_of(K);
+    // (one bucket job; the one-wave-per-window kernel sorts up to 65 535 points per window)
+    if (K > BUCKET_TERMS_MAX || (bits < bucket_split_bits && K > 65535u)) return false;
+    const uint32_t T = (B + g - 1) / g, Tpad = (T + 63u) & ~63u, L = g * l.nb, nblk = (L + CW_BLOCK - 1) / CW_BLOCK;
+    if ((uint64_t)T * g >= ((uint64_t)1 << 31) || (uint64_t)T * K >= ((uint64_t)1 << 32)) return false;
+    rt::Stream s = ctx->stream;
+    build_screen_plan(l, c.gi, g, bits);
+    ChainPlan& p = scr.plan;
+    const uint32_t nterms = p.K + p.nfix;
+    scr.w.fw = G_::FW;
+    scr.w.ensure(T, 1, 1, std::max(p.nJ, 8u), 0, 0, nwin, 4, s, 0);
+    scr.seeds.alloc((size_t)8 * L * T, s, false);
+    scr.dig.alloc((size_t)nblk * 8 * Tpad, s, false);
+    scr.cw.alloc((size_t)L * Tpad * 8, s, false);
+    scr.cs.alloc((size_t)nterms * Tpad * 8, s);
+    scr.d16.alloc((size_t)p.dev.b_dig_bytes * Tpad, s);
+    scr.tile.alloc((size_t)T * K * G_::PW, s, false);
+    scr.part.alloc(T, s, false);
+    scr.gbad.alloc(T, s, false);
+    if (!scr.flag.n) scr.flag.alloc(1, s);
+    rt::dzero(scr.part.p, (size_t)T * 4, s);
+    rt::dzero(scr.flag.p, 4, s);
+    // weights
+    ScreenDigestArgs da{w.seed.p, w.S.p, scr.seeds.p, w.Bpad, L * T, B, g, T, l.nb, l.z};
+    MP_RUN(k_screen_digest, C, T * g, 1, da);
+    ChainWeightsArgs wa{scr.seeds.p, scr.cw.p, scr.dig.p, L * T, Tpad, T, L};
+    MP_RUN(k_chain_digest, C, T, nblk, wa);
+    MP_RUN(k_chain_weights, C, T, nblk, wa);
+    // one scalar per point / run of G, the points as one run per group, ONE bucket MSM + fixed-base part per group
+    ScreenScalArgs sa{w.S.p, w.P.p, scr.cw.p, scr.cs.p, scr.dterms.p, w.Bpad, Tpad, B, g, l.nb};
+    MP_RUN(k_screen_scalars, C, T, nterms, sa);
+    ScreenTileArgs ta{w.P.p, scr.tile.p, {0, 0, 0, 0, 0, 0, 0, 0}, w.Bpad, B, g, per};
+    for (uint32_t y = 0; y < per; ++y) ta.pslot[y] = scr.pslot[y];
+    MP_RUN(k_screen_tile, C, T * g, per, ta);
+    run_equation_msm(scr.w, p.dev, scr.cs.p, scr.d16.p, T, "sigma screening: too many groups for one launch", scr.tile.p, p.K);
+    ScreenVerdictArgs va{scr.w.J.p, w.status.p, scr.part.p, scr.gbad.p, scr.flag.p, scr.w.Bpad, B, g};
+    MP_RUN(k_screen_check, C, B, 1, va);
+    MP_RUN(k_screen_verdict, C, T, 1, va);
+    MP_RUN(k_screen_mark, C, B, 1, va);
+    scr.stats[0] += B;
+    scr.stats[1] += T;
+    uint32_t flag = 0;
+    rt::d2h(&flag, scr.flag.p, 4, s);
+    rt::stream_sync(s);
+    if (!flag) return true;
+    // some group failed: ITS lanes, compacted, through the verifier's per-proof phase; everybody else's word stands
+    std::vector<uint32_t> hbad(T), hidx;
+    rt::d2h(hbad.data(), scr.gbad.p, (size_t)T * 4, s);
+    rt::stream_sync(s);
+    for (uint32_t t = 0; t < T; ++t)
+      if (hbad[t]) {
+        scr.stats[2] += 1;
+        for (uint64_t b = (uint64_t)t * g; b < std::min<uint64_t>((uint64_t)(t + 1) * g, B); ++b) hidx.push_back((uint32_t)b);
+      }
+    const uint32_t nsub = (uint32_t)hidx.size();
+    scr.stats[3] += nsub;
+    Workspace& rw = scr.rw;
+    rw.fw = G_::FW;
+    rw.ensure(nsub, 6, c.nP, c.nJ, c.nD, c.nT, nwin, 4, s);
+    scr.idx.alloc(nsub, s, false);
+    rt::h2d(scr.idx.p, hidx.data(), (size_t)nsub * 4, s);
+    ScreenGatherArgs ga{w.P.p, w.S.p, w.status.p, rw.P.p, rw.S.p, rw.status.p, scr.idx.p, w.Bpad, rw.Bpad, 3 * l.nb, 6};
+    MP_RUN(k_screen_gather, C, nsub, 3 * l.nb + 6 + 1, ga);
+    run_phase(c.vdev, rw, nsub);
+    SigmaVerdictArgs sv{rw.J.p, rw.status.p, l, rw.Bpad, c.fail_code};
+    MP_RUN(k_sigma_verdict, C, nsub, 1, sv);
+    ScatterStatusArgs ss{rw.status.p, w.status.p, scr.idx.p};
+    MP_RUN(k_scatter_status, C, nsub, 1, ss);
+    rt::stream_sync(s);      // (idx[] was uploaded from pageable memory)
+    return true;
+  }
+
   // ---------------------------------------------------------------- sigma protocols
   void sigma_host(bool prove, size_t B_, uint32_t nb, const uint8_t* bases, const uint8_t* publics, const uint8_t* witness,
                   const uint8_t* fs_init, const uint8_t* seeds, uint8_t* proofs, int32_t* status) override {
@@ -2134,9 +2328,11 @@ struct Table : mp_table {
       check_subgroup(w, B, l.A, nb);
       SigmaFsArgs fa{f, w.S.p, w.P.p, dfs.p, l, 0};
       MP_RUN(k_sigma_fs, C, B, 1, fa);
-      run_phase(ad.dev, w, B);
-      SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, nb == 1 ? 5 : 6};
-      MP_RUN(k_sigma_verdict, C, B, 1, va);
+      if (!screen_sigma(w, B, ScreenCall{l, -1, ad.dev, 3 * nb, next_partial, ad.ph.n_dslots, ad.ph.n_tslots, nb == 1 ? 5 : 6})) {
+        run_phase(ad.dev, w, B);
+        SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, nb == 1 ? 5 : 6};
+        MP_RUN(k_sigma_verdict, C, B, 1, va);
+      }
     }
     rt::d2h(status, w.status.p, (size_t)B * 4, s);
     rt::stream_sync(s);
@@ -2277,9 +2473,11 @@ struct Table : mp_table {
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     SigmaFsArgs fa{f, w.S.p, w.P.p, op.fs.p, l, 0};
     MP_RUN(k_sigma_fs, C, B, 1, fa);
-    run_phase(op.vdev, w, B);
-    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
-    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    if (!screen_sigma(w, B, ScreenCall{l, 1, op.vdev, 6, op.nJ, op.nD, op.nT, 6})) {
+      run_phase(op.vdev, w, B);
+      SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
+      MP_RUN(k_sigma_verdict, C, B, 1, va);
+    }
     UnmaskSumArgs ua{w.P.p, w.status.p, signer, op.c1.p, op.cstat.p, op.sumJ.p, token_status, card_status, w.Bpad, (uint32_t)K, T, l.a};
     MP_RUN(k_unmask_sum, C, Cn, 1, ua);
     normalize_flat(op.sumJ.p, op.sumP.p, op.scratch.p, Cn);
@@ -2486,9 +2684,11 @@ struct Table : mp_table {
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 0};
     MP_RUN(k_sigma_fs, C, B, 1, fa);
-    run_phase(deal.vdev, w, B);
-    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
-    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    if (!screen_sigma(w, B, ScreenCall{l, 0, deal.vdev, d.nP, deal.nJ, deal.nD, deal.nT, 6})) {
+      run_phase(deal.vdev, w, B);
+      SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
+      MP_RUN(k_sigma_verdict, C, B, 1, va);
+    }
     DealFinishArgs fin{w.status.p, key_index, status, nullptr, nullptr, (uint32_t)K};
     MP_RUN(k_deal_finish, C, B, 1, fin);
   }
@@ -2582,9 +2782,11 @@ struct Table : mp_table {
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 0};
     MP_RUN(k_sigma_fs, C, B, 1, fa);
-    run_phase(deal.sdev, w, B);
-    SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 5};
-    MP_RUN(k_sigma_verdict, C, B, 1, va);
+    if (!screen_sigma(w, B, ScreenCall{l, 0, deal.sdev, make_deal_lay().nP, deal.nJ, deal.nD, deal.nT, 5})) {
+      run_phase(deal.sdev, w, B);
+      SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 5};
+      MP_RUN(k_sigma_verdict, C, B, 1, va);
+    }
     KeySumArgs ka{w.P.p, w.status.p, deal.sumJ.p, dps.p, dts.p, w.Bpad, seats, l.a};
     MP_RUN(k_key_sum, C, Tn, 1, ka);
     normalize_flat(deal.sumJ.p, deal.sumP.p, deal.scratch.p, Tn);

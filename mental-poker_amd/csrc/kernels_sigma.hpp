@@ -78,6 +78,10 @@ MP_HD void body_sigma_fs(const SigmaFsArgs& a, uint32_t b, uint32_t y) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) seed[i] = sw[i];
   fs_absorb_points<C>(a.f, a.P, b, seed, 0, 3 * l.nb);     // g.., a.., A.. are consecutive P slots
+  if (!a.prove) {      // (the verifier keeps the state: a screening pass hashes its lane digests from it -- kernels_screen.hpp)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a.f.seed[(size_t)i * a.f.Bpad + b] = seed[i];
+  }
   fs_challenges<C>(seed, a.S, a.f.Bpad, b, l.c, NO_SLOT);
   const Fe<R> c = ld_fe<R>(a.S + s_off(l.c, a.f.Bpad, b));
   if (a.prove) {

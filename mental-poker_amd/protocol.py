@@ -113,7 +113,7 @@ class DLCards:
     """`impl BarnettSmartProtocol for DLCards<C>` -- hot-path members only (setup, shuffle_and_remask,
     verify_shuffle and their batched forms).  One instance = one curve on one GPU."""
 
-    def __init__(self, curve="stark", device=0, fb_bits=8, coalesce=None):
+    def __init__(self, curve="stark", device=0, fb_bits=8, coalesce=None, sigma_screen=None):
         self.curve = curve
         self.fb_bits = fb_bits      # fixed-base window width of the table contexts (8: compact, 16: throughput)
         self.engine = _native.Engine(curve, device)
@@ -129,6 +129,15 @@ class DLCards:
         self.coalesce = coalesce
         self._params_tables = {}
         self._params_lock = threading.Lock()
+        # sigma_screen = (lanes_per_group, min_lanes): open_cards, verify_deal, verify_deal_remask and compute_aggregate_keys screen their
+        # proofs with grouped equations first (_native.Table.set_sigma_screen; lanes_per_group may be Table.SIGMA_SCREEN_AUTO) -- same
+        # results, calls of fewer than min_lanes lanes as before.  None: every proof on its own, as before.
+        if sigma_screen is not None:
+            lanes, min_lanes = sigma_screen
+            if not 0 <= int(lanes) <= _native.Table.SIGMA_SCREEN_AUTO or int(min_lanes) < 0:
+                raise CardProtocolError.io("sigma_screen = (lanes per group or SIGMA_SCREEN_AUTO, min_lanes >= 0)")
+            sigma_screen = (int(lanes), int(min_lanes))
+        self.sigma_screen = sigma_screen
 
     # -- fn setup<R: Rng>(rng, m, n) -> Result<Parameters, CardProtocolError>          [REF mod.rs:105-121]
     def setup(self, rng_seed, m, n):
@@ -165,6 +174,8 @@ class DLCards:
         if t is None:
             try:
                 t = self.engine.table(pp.m, pp.n, pp.raw, shared_key, self.fb_bits)
+                if self.sigma_screen is not None:
+                    t.set_sigma_screen(*self.sigma_screen)
             except _native.NativeError as e:
                 raise CardProtocolError.io(str(e))
             if len(self._tables) >= 4:
