@@ -49,7 +49,7 @@ SOURCES = ["capi.hip"] + [f % c for c in ("stark", "bn254", "secp256k1", "bls12_
 def build(verbose=False):
     """compile the HIP engine for gfx950 in-tree -> mental-poker_amd/libmpshuffle.so
     (one translation unit per curve, compiled in parallel, objects cached under csrc/_obj), and beside it the test tools
-    tools/quadcheck/quad_check and tools/primcheck/libprimcheck.so"""
+    tools/quadcheck/quad_check, tools/primcheck/libprimcheck.so and tools/fscheck/libfscheck.so"""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(HERE, "csrc")
     objdir = os.path.join(csrc, "_obj")
@@ -93,15 +93,19 @@ def build(verbose=False):
     probe_src = os.path.join(probe_dir, "prim_check.hip")
     probe_lib = os.path.join(probe_dir, "libprimcheck.so")
 
-    def compile_probe(curve_id):
-        """tools/primcheck/prim_check.hip: one field / group operation per lane, for tests/test_gpu_primitives.py.  One object per curve,
-        with EXACTLY the library's flags (the code generation under test is the library's); a shared object of its own, nothing of it
-        goes into libmpshuffle.so"""
+    fs_dir = os.path.join(ROOT, "tools", "fscheck")
+    fs_src = os.path.join(fs_dir, "fs_check.hip")
+    fs_lib = os.path.join(fs_dir, "libfscheck.so")
+
+    def compile_probe(curve_id, probe_dir=probe_dir, probe_src=probe_src, stem="prim_check", macro="PRIM_CURVE"):
+        """tools/primcheck/prim_check.hip: one field / group operation per lane, for tests/test_gpu_primitives.py; tools/fscheck/fs_check.hip:
+        the Fiat-Shamir layer and the screening weights, for tests/test_gpu_fs.py.  One object per curve, with EXACTLY the library's flags
+        (the code generation under test is the library's); shared objects of their own, nothing of them goes into libmpshuffle.so"""
         os.makedirs(os.path.join(probe_dir, "_obj"), exist_ok=True)
-        obj = os.path.join(probe_dir, "_obj", "prim_check_%d.o" % curve_id)
+        obj = os.path.join(probe_dir, "_obj", "%s_%d.o" % (stem, curve_id))
         if os.path.exists(obj) and os.path.getmtime(obj) >= max(hdr_time, os.path.getmtime(probe_src)):
             return obj, False
-        cmd = [hipcc] + flags + ["-DPRIM_CURVE=%d" % curve_id, "-I", csrc, "-c", probe_src, "-o", obj]
+        cmd = [hipcc] + flags + ["-D%s=%d" % (macro, curve_id), "-I", csrc, "-c", probe_src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
@@ -109,11 +113,12 @@ def build(verbose=False):
 
     # The library's translation units are queued first and the library is linked as soon as THEY are done; the probe's objects
     # share the pool and are collected afterwards, so the library never waits for the probe's link (they do compete for cores).
-    ex = ThreadPoolExecutor(max_workers=len(SOURCES) + 1 + len(CURVE_IDS))
+    ex = ThreadPoolExecutor(max_workers=len(SOURCES) + 1 + 2 * len(CURVE_IDS))
     try:
         res_f = [ex.submit(compile_one, s) for s in SOURCES]
         chk = ex.submit(compile_check)
         probe_f = [ex.submit(compile_probe, k) for k in sorted(CURVE_IDS.values())] if os.path.exists(probe_src) else []
+        fs_f = [ex.submit(compile_probe, k, fs_dir, fs_src, "fs_check", "FS_CURVE") for k in sorted(CURVE_IDS.values())] if os.path.exists(fs_src) else []
         res = [f.result() for f in res_f]
         objs = [r[0] for r in res]
         if any(r[1] for r in res) or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(o) for o in objs):
@@ -123,14 +128,16 @@ def build(verbose=False):
             subprocess.check_call(cmd)
         chk.result()
         probe = [f.result() for f in probe_f]      # (a probe that does not compile fails the build: its tests do not skip)
+        fs_probe = [f.result() for f in fs_f]
     finally:
         ex.shutdown(wait=True)
-    if probe and (any(r[1] for r in probe) or not os.path.exists(probe_lib)
-                  or os.path.getmtime(probe_lib) < max(os.path.getmtime(r[0]) for r in probe)):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", probe_lib] + [r[0] for r in probe]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+    for objs_p, lib_p in ((probe, probe_lib), (fs_probe, fs_lib)):
+        if objs_p and (any(r[1] for r in objs_p) or not os.path.exists(lib_p)
+                       or os.path.getmtime(lib_p) < max(os.path.getmtime(r[0]) for r in objs_p)):
+            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_p] + [r[0] for r in objs_p]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.check_call(cmd)
     # multiply-add counts of the compiled field arithmetic (bench.py's int_mul roofline): regenerated with the library
     mc = os.path.join(HERE, "mad_counts.json")
     gen = os.path.join(ROOT, "tools", "gen_mad_counts.py")

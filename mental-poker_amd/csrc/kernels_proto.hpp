@@ -810,6 +810,27 @@ struct VerifyFsArgs {
   VerifyLay l;
   uint32_t merge;      // 1: also derive the weights r_k of the merged equation (verifier-only randomness)
 };
+// Weights of the merged equation: they must depend on EVERY proof element, including the final responses that the
+// transcript itself never absorbs (a prover who knew r could trade errors between equations through them): absorb
+// the 5n+9 response scalars (slots 0 .. 5n+8, wire order) and squeeze one weight per check id.  seed <- the transcript's
+// last state, also left in f.seed: chain verification hashes it.
+template <class C>
+MP_HD void fs_merge_weights(const FsDev& f, uint32_t* S, const VerifyLay& l, uint32_t b, uint32_t seed[8]) {
+  typedef typename C::FrP R;
+  StageWriter w = stage_begin(f.stage, f.Bpad, b);
+  for (uint32_t i = 0; i < 5 * l.n + 9; ++i) {
+    uint32_t k[8];
+    fe_to_canonical<R>(ld_fe<R>(S + s_off(l.zabar + i, f.Bpad, b)), k);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) stage_word(w, k[t]);
+  }
+  fs_finish_absorb(w, seed);
+  FrStream st;
+  frstream_init(st, seed);
+  for (uint32_t k = 0; k < (uint32_t)VC_COUNT; ++k) st_fe<R>(S + s_off(l.mr + k, f.Bpad, b), frstream_next<R>(st));
+#pragma unroll
+  for (int t = 0; t < 8; ++t) f.seed[(size_t)t * f.Bpad + b] = seed[t];
+}
 template <class C>
 MP_HD void body_verify_fs(const VerifyFsArgs& a, uint32_t b, uint32_t y) {
   const VerifyLay& l = a.l;
@@ -830,25 +851,7 @@ MP_HD void body_verify_fs(const VerifyFsArgs& a, uint32_t b, uint32_t y) {
   fs_challenges<C>(seed, S, f.Bpad, b, l.svx, NO_SLOT);
   fs_absorb_points<C>(f, P, b, seed, l.mecA0, 1 + 2 * m + 4 * m);  // mecA0, mecB[2m], meE[4m] consecutive
   fs_challenges<C>(seed, S, f.Bpad, b, l.mx, NO_SLOT);
-  if (a.merge) {
-    // Weights of the merged equation: they must depend on EVERY proof element, including the final responses that the
-    // transcript itself never absorbs (a prover who knew r could trade errors between equations through them): absorb
-    // the 5n+9 response scalars (slots 0 .. 5n+8, wire order) and squeeze one weight per check id.
-    typedef typename C::FrP R;
-    StageWriter w = stage_begin(f.stage, f.Bpad, b);
-    for (uint32_t i = 0; i < 5 * l.n + 9; ++i) {
-      uint32_t k[8];
-      fe_to_canonical<R>(ld_fe<R>(S + s_off(l.zabar + i, f.Bpad, b)), k);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) stage_word(w, k[t]);
-    }
-    fs_finish_absorb(w, seed);
-    FrStream st;
-    frstream_init(st, seed);
-    for (uint32_t k = 0; k < (uint32_t)VC_COUNT; ++k) st_fe<R>(S + s_off(l.mr + k, f.Bpad, b), frstream_next<R>(st));
-#pragma unroll
-    for (int t = 0; t < 8; ++t) f.seed[(size_t)t * f.Bpad + b] = seed[t];     // the transcript's last state: chain verification hashes it
-  }
+  if (a.merge) fs_merge_weights<C>(f, S, l, b, seed);
 }
 MP_KERNEL(k_verify_fs, VerifyFsArgs, body_verify_fs)
 
@@ -975,9 +978,42 @@ struct FsqVerifyArgs {
   VerifyFsArgs v;
   FsqGeom g;
 };
+// the weights of the merged equation (fs_merge_weights) on the lanes of a proof: the 5n + 9 response scalars, 8 aligned words each
+template <class C, class W>
+MP_HD void fsq_merge_weights(W& wv, const FsDev& f, const FsqGeom& g, uint32_t wid, uint32_t* S, const VerifyLay& l, PerLane<B2sSeed>& seed) {
+  typedef typename C::FrP R;
+  const uint32_t nsc = 5 * l.n + 9;
+  PerLane<const uint32_t*> base;
+  wv.lanes([&](uint32_t ln) {
+    const FsqLane q = fsq_lane(g, wid, ln);
+    base[ln] = f.stage + q.b;
+    if (!q.live) return;
+    for (uint32_t i = q.sub; i < nsc; i += g.lpp) {
+      uint32_t k[8];
+      fe_to_canonical<R>(ld_fe<R>(S + s_off(l.zabar + i, f.Bpad, q.b)), k);
+      StageWriter w = stage_begin_at(f.stage, f.Bpad, q.b, 8 * i);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) stage_word(w, k[t]);
+    }
+    if (q.sub == 0) {
+      StageWriter w = stage_begin_at(f.stage, f.Bpad, q.b, 8 * nsc);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) stage_word(w, seed[ln].s[t]);
+    }
+  });
+  wv.sync_global();
+  blake2s_staged_quad(wv, base, f.Bpad, 32 * nsc + 32, seed);
+  wv.lanes([&](uint32_t ln) {
+    const FsqLane q = fsq_lane(g, wid, ln);
+    if (!q.live || q.sub != 0) return;
+    FrStream st;
+    frstream_init(st, seed[ln].s);
+    for (uint32_t k = 0; k < (uint32_t)VC_COUNT; ++k) st_fe<R>(S + s_off(l.mr + k, f.Bpad, q.b), frstream_next<R>(st));
+    fs_store_seed(f, q.b, seed[ln].s);      // the transcript's last state: chain verification hashes it
+  });
+}
 template <class C, class W>
 MP_HD void body_fsq_verify(const FsqVerifyArgs& a, uint32_t wid, W& wv) {
-  typedef typename C::FrP R;
   const VerifyLay& l = a.v.l;
   const uint32_t m = l.m;
   const FsDev& f = a.v.st.f;
@@ -997,37 +1033,7 @@ MP_HD void body_fsq_verify(const FsqVerifyArgs& a, uint32_t wid, W& wv) {
   fsq_challenges<C>(wv, f, g, wid, S, seed, l.svx, NO_SLOT);
   fsq_absorb_points<C>(wv, f, g, wid, P, l.mecA0, 1 + 2 * m + 4 * m, 0, 0, seed);
   fsq_challenges<C>(wv, f, g, wid, S, seed, l.mx, NO_SLOT);
-  if (a.v.merge) {      // the weights of the merged equation (body_verify_fs): the 5n + 9 response scalars, 8 aligned words each
-    const uint32_t nsc = 5 * l.n + 9;
-    PerLane<const uint32_t*> base;
-    wv.lanes([&](uint32_t ln) {
-      const FsqLane q = fsq_lane(g, wid, ln);
-      base[ln] = f.stage + q.b;
-      if (!q.live) return;
-      for (uint32_t i = q.sub; i < nsc; i += g.lpp) {
-        uint32_t k[8];
-        fe_to_canonical<R>(ld_fe<R>(S + s_off(l.zabar + i, f.Bpad, q.b)), k);
-        StageWriter w = stage_begin_at(f.stage, f.Bpad, q.b, 8 * i);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) stage_word(w, k[t]);
-      }
-      if (q.sub == 0) {
-        StageWriter w = stage_begin_at(f.stage, f.Bpad, q.b, 8 * nsc);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) stage_word(w, seed[ln].s[t]);
-      }
-    });
-    wv.sync_global();
-    blake2s_staged_quad(wv, base, f.Bpad, 32 * nsc + 32, seed);
-    wv.lanes([&](uint32_t ln) {
-      const FsqLane q = fsq_lane(g, wid, ln);
-      if (!q.live || q.sub != 0) return;
-      FrStream st;
-      frstream_init(st, seed[ln].s);
-      for (uint32_t k = 0; k < (uint32_t)VC_COUNT; ++k) st_fe<R>(S + s_off(l.mr + k, f.Bpad, q.b), frstream_next<R>(st));
-      fs_store_seed(f, q.b, seed[ln].s);      // the transcript's last state: chain verification hashes it
-    });
-  }
+  if (a.v.merge) fsq_merge_weights<C>(wv, f, g, wid, S, l, seed);
 }
 MP_WAVE_KERNEL(k_fsq_verify, FsqVerifyArgs, body_fsq_verify)
 
