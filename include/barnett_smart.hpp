@@ -5,6 +5,7 @@
 //   [REF barnett-smart-card-protocol/src/discrete_log_cards/mod.rs:105-121, 380-443].
 // Result<T, E> becomes: return T, throw E.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -203,6 +204,77 @@ class DLCardsT {
     return a;
   }
 
+  // Secrets drawn on the device from seeds (mpshuffle.h "secrets drawn on the device from seeds", the stream is defined there): one
+  // fresh 32-byte CSPRNG seed per shuffle / per player, never reused, and all a caller has to store.  Pass-throughs: status words are
+  // returned, not thrown.
+  struct ShuffleWitnesses {
+    std::vector<Permutation> permutations;          // one per seed, m*n entries each
+    std::vector<std::vector<Scalar>> masking_factors;
+  };
+  struct SeededShuffles {
+    std::vector<std::vector<MaskedCard>> decks;
+    std::vector<ZKProofShuffle> proofs;
+    std::vector<int32_t> status;
+  };
+  struct PlayerKeys {
+    std::vector<PublicKey> keys;
+    std::vector<Scalar> secret_keys;
+    std::vector<ZKProofKeyOwnership> proofs;        // empty without fs_init
+    std::vector<int32_t> status;
+  };
+  // [REF examples/round.rs:265-266] for many shuffles: what shuffle_and_remask_batch_seeded uses for the same seeds
+  ShuffleWitnesses sample_shuffle_witnesses(const std::vector<std::array<uint8_t, 32>>& seeds, const Parameters& pp) {
+    const size_t N = (size_t)pp.m * pp.n, B = seeds.size();
+    if (!B) throw CardProtocolError("sample_shuffle_witnesses: at least one seed");
+    bind_any(pp, generator(pp));
+    std::vector<Scalar> sc(B * N);
+    std::vector<uint32_t> pm(B * N);
+    if (mp_sample_secrets_batch(table_, B, seeds[0].data(), (uint32_t)N, (uint32_t)N, sc[0].data(), pm.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    ShuffleWitnesses w{std::vector<Permutation>(B), std::vector<std::vector<Scalar>>(B)};
+    for (size_t b = 0; b < B; ++b) {
+      w.permutations[b].mapping.assign(pm.begin() + b * N, pm.begin() + (b + 1) * N);
+      w.masking_factors[b].assign(sc.begin() + b * N, sc.begin() + (b + 1) * N);
+    }
+    return w;
+  }
+  // shuffle_and_remask for many decks under one aggregate key, the witness of proof b drawn from seeds[b], which is also its prover seed
+  SeededShuffles shuffle_and_remask_batch_seeded(const std::vector<std::array<uint8_t, 32>>& seeds, const Parameters& pp, const PublicKey& shared_key,
+                                                 const std::vector<std::vector<MaskedCard>>& decks) {
+    const size_t N = (size_t)pp.m * pp.n, B = seeds.size();
+    if (!B || decks.size() != B) throw CardProtocolError("shuffle_and_remask_batch_seeded: one deck per seed, at least one");
+    std::vector<MaskedCard> in(B * N), out(B * N);
+    for (size_t b = 0; b < B; ++b) {
+      if (decks[b].size() != N) throw CardProtocolError("shuffle_and_remask_batch_seeded: a deck has m*n cards");
+      std::copy(decks[b].begin(), decks[b].end(), in.begin() + b * N);
+    }
+    bind(pp, shared_key);
+    const size_t psz = mp_proof_size_curve(curve_, pp.m, pp.n);
+    std::vector<uint8_t> proofs(B * psz);
+    SeededShuffles r{std::vector<std::vector<MaskedCard>>(B), std::vector<ZKProofShuffle>(B), std::vector<int32_t>(B)};
+    if (mp_shuffle_and_remask_batch_seeded(table_, B, nullptr, in[0].data(), seeds[0].data(), out[0].data(), proofs.data(), r.status.data(),
+                                           nullptr, nullptr) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    for (size_t b = 0; b < B; ++b) {
+      r.decks[b].assign(out.begin() + b * N, out.begin() + (b + 1) * N);
+      r.proofs[b].assign(proofs.begin() + b * psz, proofs.begin() + (b + 1) * psz);
+    }
+    return r;
+  }
+  // player_keygen [REF mod.rs:123-130] for many players; with fs_init (one Blake2s("Key Ownership Proof" || player_public_info) per seed)
+  // also prove_key_ownership [REF mod.rs:132-149] under the prover seed seeds[k]
+  PlayerKeys player_keygen_batch(const std::vector<std::array<uint8_t, 32>>& seeds, const Parameters& pp,
+                                 const std::vector<std::array<uint8_t, 32>>& fs_init = {}) {
+    const size_t K = seeds.size();
+    if (!K || (!fs_init.empty() && fs_init.size() != K)) throw CardProtocolError("player_keygen_batch: at least one seed; one digest per seed, or none");
+    bind_any(pp, generator(pp));
+    PlayerKeys p{std::vector<PublicKey>(K), std::vector<Scalar>(K), std::vector<ZKProofKeyOwnership>(fs_init.size()), std::vector<int32_t>(K)};
+    if (mp_keygen_batch(table_, K, seeds[0].data(), fs_init.empty() ? nullptr : fs_init[0].data(), p.keys[0].data(), p.secret_keys[0].data(),
+                        fs_init.empty() ? nullptr : p.proofs[0].data(), p.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return p;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
 
  private:
@@ -228,6 +300,12 @@ class DLCardsT {
                              proofs[0].data(), status.data()) != MP_OK)
       throw CardProtocolError(mp_last_error());
     return status;
+  }
+  // G of the parameters: the key of a table that is bound for calls that use no key
+  static PublicKey generator(const Parameters& pp) {
+    PublicKey g{};
+    if (pp.raw.size() >= PB) std::copy(pp.raw.begin(), pp.raw.begin() + PB, g.begin());
+    return g;
   }
   // a table of pp, whatever its key: the calls that use only G of the parameters keep the one that is bound
   void bind_any(const Parameters& pp, const PublicKey& pk) {

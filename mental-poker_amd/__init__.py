@@ -6,7 +6,7 @@ Everything is computed by libmpshuffle.so (hand-written HIP for gfx950); importi
 creating an engine does not (no CPU fallback)."""
 from . import _native, canonical
 from ._native import Engine, NativeError, NoDeviceError, Serializer, build, load
-from .protocol import (CardProtocolError, ChaCha20Rng, CryptoError, DLCards, Parameters, Permutation, fr_rand)
+from .protocol import (CardProtocolError, ChaCha20Rng, CryptoError, DLCards, Parameters, Permutation, fr_rand, secret_stream)
 
 __all__ = ["Engine", "Serializer", "NativeError", "NoDeviceError", "build", "load", "DLCards", "Parameters", "Permutation",
-           "CryptoError", "CardProtocolError", "ChaCha20Rng", "fr_rand", "_native", "canonical"]
+           "CryptoError", "CardProtocolError", "ChaCha20Rng", "fr_rand", "secret_stream", "_native", "canonical"]

@@ -27,6 +27,8 @@ SYMBOLS = [
     "mp_sigma_verify_batch", "mp_blake2s", "mp_reveal_batch", "mp_unmask_batch", "mp_unmask_batch_dev",
     "mp_mask_batch", "mp_verify_mask_batch", "mp_verify_mask_batch_dev", "mp_aggregate_keys_batch",
     "mp_set_sigma_screen", "mp_sigma_screen_stats",
+    "mp_sample_secrets_batch", "mp_sample_secrets_batch_dev", "mp_shuffle_and_remask_batch_seeded", "mp_shuffle_and_remask_batch_seeded_dev",
+    "mp_keygen_batch",
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
@@ -255,6 +257,11 @@ def bind(cdll):
     cdll.mp_verify_mask_batch_dev.argtypes = [c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
     cdll.mp_aggregate_keys_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, u8p, i32p, i32p]
     cdll.mp_set_sigma_screen.argtypes = [c.c_void_p, c.c_uint32, c.c_size_t]
+    cdll.mp_sample_secrets_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, c.c_uint32, c.c_uint32, u8p, u32p]
+    cdll.mp_sample_secrets_batch_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p]
+    cdll.mp_shuffle_and_remask_batch_seeded.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, u8p, u8p, i32p, u32p, u8p]
+    cdll.mp_shuffle_and_remask_batch_seeded_dev.argtypes = [c.c_void_p, c.c_size_t] + [c.c_void_p] * 8
+    cdll.mp_keygen_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, u8p, u8p, i32p]
     cdll.mp_sigma_screen_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
     for fn, at in (("mp_serialized_point_size", [c.c_int]), ("mp_serialized_deck_size", [c.c_int, c.c_size_t]),
                    ("mp_serialized_params_size", [c.c_int, c.c_uint32]), ("mp_serialized_proof_size", [c.c_int, c.c_uint32, c.c_uint32])):
@@ -775,6 +782,59 @@ class Table:
         ts = (ctypes.c_int32 * max(tables, 1))()
         self.eng._chk(self.lib.mp_aggregate_keys_batch(self.h, tables, P, _in(keys), _in(proofs), _in(fs_init), out, ps, ts))
         return bytes(out)[:tables * self.pb], list(ps)[:B], list(ts)[:tables]
+
+    # ---- secrets from seeds ("mpshuffle secret stream v1", include/mpshuffle.h): one 32-byte seed per lane
+    def sample_secrets_batch(self, seeds, S, P):
+        """L seeds -> (L * S wire scalars as bytes, list of L * P permutation entries)"""
+        L = len(seeds) // 32
+        self._need("seeds", len(seeds), L * 32)
+        sc = (ctypes.c_uint8 * max(L * S * 32, 1))()
+        pm = (ctypes.c_uint32 * max(L * P, 1))()
+        self.eng._chk(self.lib.mp_sample_secrets_batch(self.h, L, _in(seeds), S, P, sc if S else None, pm if P else None))
+        return bytes(sc)[:L * S * 32], list(pm)[:L * P]
+
+    def sample_secrets_batch_dev(self, L, d_seeds, S, P, d_out_scalars, d_out_perms):
+        """the same with device pointers; the outputs are final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_sample_secrets_batch_dev(self.h, L, d_seeds, S, P, d_out_scalars, d_out_perms))
+
+    def shuffle_and_remask_batch_seeded(self, decks, seeds, keys=None, witness=False):
+        """B proofs whose masking factors and permutations are drawn on the device from seeds[b] (also the prover seed); keys: None = the
+        table's key, else B wire points -> (decks, proofs, status), with witness=True also (permutation entries, masking factors)"""
+        B, N = len(seeds) // 32, self.N
+        self._need("seeds", len(seeds), B * 32)
+        self._need("decks", len(decks), B * N * self.cb)
+        if keys is not None:
+            self._need("keys", len(keys), B * self.pb)
+        out_d = (ctypes.c_uint8 * max(B * N * self.cb, 1))()
+        out_p = (ctypes.c_uint8 * max(B * self.proof_bytes, 1))()
+        st = (ctypes.c_int32 * max(B, 1))()
+        pm = (ctypes.c_uint32 * max(B * N, 1))() if witness else None
+        rho = (ctypes.c_uint8 * max(B * N * 32, 1))() if witness else None
+        self.eng._chk(self.lib.mp_shuffle_and_remask_batch_seeded(self.h, B, _in(keys) if keys is not None else None, _in(decks), _in(seeds),
+                                                                  out_d, out_p, st, pm, rho))
+        res = bytes(out_d)[:B * N * self.cb], bytes(out_p)[:B * self.proof_bytes], list(st)[:B]
+        return res + (list(pm)[:B * N], bytes(rho)[:B * N * 32]) if witness else res
+
+    def shuffle_and_remask_batch_seeded_dev(self, B, d_keys, d_decks, d_seeds, d_out_decks, d_out_proofs, d_status, d_out_perms=None,
+                                            d_out_factors=None):
+        """the same with device pointers (d_keys / d_out_perms / d_out_factors may be None); final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_shuffle_and_remask_batch_seeded_dev(self.h, B, d_keys, d_decks, d_seeds, d_out_decks, d_out_proofs, d_status,
+                                                                      d_out_perms, d_out_factors))
+
+    def keygen_batch(self, seeds, fs_init=None):
+        """K players: sk = the stream's single scalar, pk = sk G; with fs_init (K * 32 bytes) also the proofs of key ownership under the
+        prover seeds `seeds` -> (public keys, secret keys, proofs or None, status)"""
+        K = len(seeds) // 32
+        self._need("seeds", len(seeds), K * 32)
+        if fs_init is not None:
+            self._need("fs_init", len(fs_init), K * 32)
+        psz = self.pb + 32
+        pk = (ctypes.c_uint8 * max(K * self.pb, 1))()
+        sk = (ctypes.c_uint8 * max(K * 32, 1))()
+        prf = (ctypes.c_uint8 * max(K * psz, 1))() if fs_init is not None else None
+        st = (ctypes.c_int32 * max(K, 1))()
+        self.eng._chk(self.lib.mp_keygen_batch(self.h, K, _in(seeds), _in(fs_init) if fs_init is not None else None, pk, sk, prf, st))
+        return bytes(pk)[:K * self.pb], bytes(sk)[:K * 32], bytes(prf)[:K * psz] if prf is not None else None, list(st)[:K]
 
     def set_io_chunk(self, proofs):
         """proofs per pipelined chunk of the host-buffer entry points (0 = default 65536)"""

@@ -772,10 +772,13 @@ static void io_events(mp_io_stage& st) {
   }
 }
 
+// seeded (mp_shuffle_and_remask_batch_seeded): no witness comes from the host -- every chunk's masking factors and permutations are sampled
+// from its prover seeds into the staging buffers the unseeded call uploads them to, and go back to the host only if asked for
 static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const uint8_t* decks, const uint8_t* masking_factors,
                             const uint32_t* permutations, const uint8_t* prover_seeds, uint8_t* out_decks,
-                            uint8_t* out_proofs, int32_t* status) {
-  if (!t || !B || !decks || !masking_factors || !permutations || !prover_seeds || !out_decks || !out_proofs || !status)
+                            uint8_t* out_proofs, int32_t* status, bool seeded = false, uint32_t* out_perms = nullptr,
+                            uint8_t* out_factors = nullptr) {
+  if (!t || !B || !decks || (!seeded && (!masking_factors || !permutations)) || !prover_seeds || !out_decks || !out_proofs || !status)
     return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch: bad argument");
   if (t->keyless && !keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: use the _keys entry points");
   MP_TRY
@@ -800,8 +803,10 @@ static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const ui
     const size_t o = first[k], c = sched[k];
     if (st.used) rt::stream_wait(up, st.done);          // the kernels of chunk k-2 have consumed these buffers
     rt::h2d(st.in0.p, decks + o * dsz, c * dsz, up);
-    rt::h2d(st.in1.p, masking_factors + o * N * 32, c * N * 32, up);
-    rt::h2d(st.perm.p, permutations + o * N, c * N * 4, up);
+    if (!seeded) {
+      rt::h2d(st.in1.p, masking_factors + o * N * 32, c * N * 32, up);
+      rt::h2d(st.perm.p, permutations + o * N, c * N * 4, up);
+    }
     rt::h2d(st.in2.p, prover_seeds + o * 32, c * 32, up);
     if (keys) rt::h2d(st.keys.p, keys + o * t->point_bytes, c * t->point_bytes, up);
     rt::event_record(st.up, up);
@@ -812,6 +817,7 @@ static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const ui
     const size_t o = first[k], c = sched[k];
     rt::stream_wait(s, st.up);
     if (st.used) rt::stream_wait(s, st.down);            // results of chunk k-2 have left the output buffers
+    if (seeded) t->sample_dev(c, st.in2.p, (uint32_t)N, (uint32_t)N, st.in1.p, st.perm.p);
     t->prove_dev(c, st.in0.p, st.in1.p, st.perm.p, st.in2.p, st.out0.p, st.out1.p, st.status.p, keys ? st.keys.p : nullptr);
     rt::event_record(st.done, s);
     if (k + 1 < nchunks) upload(k + 1);
@@ -819,6 +825,8 @@ static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const ui
     rt::d2h(out_decks + o * dsz, st.out0.p, c * dsz, down);
     rt::d2h(out_proofs + o * psz, st.out1.p, c * psz, down);
     rt::d2h(status + o, st.status.p, c * 4, down);
+    if (out_perms) rt::d2h(out_perms + o * N, st.perm.p, c * N * 4, down);
+    if (out_factors) rt::d2h(out_factors + o * N * 32, st.in1.p, c * N * 32, down);
     rt::event_record(st.down, down);
     st.used = true;
   }
@@ -1183,6 +1191,68 @@ int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_
   MP_TRY
   MP_ENTER(t->ctx);
   t->aggregate_keys_host(tables, P, keys, proofs, fs_init, out_keys, player_status, table_status);
+  return MP_OK;
+  MP_CATCH
+}
+
+// ---- secrets from seeds: "mpshuffle secret stream v1" (kernels_sample.hpp; engine_core.hpp "secrets from seeds")
+static const size_t SAMPLE_MAX_LANES = 1048576;
+static const uint32_t SAMPLE_MAX_COUNT = 4096;
+static bool sample_shape_ok(size_t L, uint32_t S, uint32_t P) {
+  return L >= 1 && L <= SAMPLE_MAX_LANES && S <= SAMPLE_MAX_COUNT && P <= SAMPLE_MAX_COUNT && (S || P);
+}
+static const char* const SAMPLE_SHAPE = "1 <= L <= 1 048 576, S <= 4 096, P <= 4 096, not both 0";
+int mp_sample_secrets_batch(mp_table* t, size_t L, const uint8_t* seeds, uint32_t S, uint32_t P, uint8_t* out_scalars, uint32_t* out_perms) {
+  if (!t || !seeds || (S && !out_scalars) || (P && !out_perms)) return fail(MP_ERR_BAD_ARGUMENT, "mp_sample_secrets_batch: null argument");
+  if (!sample_shape_ok(L, S, P)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_sample_secrets_batch: ") + SAMPLE_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->sample_host(L, seeds, S, P, out_scalars, out_perms);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_sample_secrets_batch_dev(mp_table* t, size_t L, const void* d_seeds, uint32_t S, uint32_t P, void* d_out_scalars, void* d_out_perms) {
+  if (!t || !d_seeds || (S && !d_out_scalars) || (P && !d_out_perms)) return fail(MP_ERR_BAD_ARGUMENT, "mp_sample_secrets_batch_dev: null argument");
+  if (!sample_shape_ok(L, S, P)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_sample_secrets_batch_dev: ") + SAMPLE_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->sample_dev(L, (const uint8_t*)d_seeds, S, P, (uint8_t*)d_out_scalars, (uint32_t*)d_out_perms);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_shuffle_and_remask_batch_seeded(mp_table* t, size_t B, const uint8_t* shared_keys, const uint8_t* decks, const uint8_t* seeds,
+                                       uint8_t* out_decks, uint8_t* out_proofs, int32_t* status, uint32_t* out_perms, uint8_t* out_factors) {
+  return prove_batch_host(t, B, shared_keys, decks, nullptr, nullptr, seeds, out_decks, out_proofs, status, true, out_perms, out_factors);
+}
+int mp_shuffle_and_remask_batch_seeded_dev(mp_table* t, size_t B, const void* d_keys, const void* d_decks, const void* d_seeds,
+                                           void* d_out_decks, void* d_out_proofs, void* d_status, void* d_out_perms, void* d_out_factors) {
+  if (!t || !B || !d_decks || !d_seeds || !d_out_decks || !d_out_proofs || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch_seeded_dev: bad argument");
+  if (t->keyless && !d_keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: pass one key per proof");
+  if (B > SAMPLE_MAX_LANES) return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch_seeded_dev: at most 1 048 576 proofs per call");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  rt::Stream s = t->ctx->stream;
+  const size_t N = t->N;
+  // the witness stays in the table's workspace unless the caller wants it
+  if (!d_out_factors) t->seeded_rho.alloc(B * N * 32, s, false);
+  if (!d_out_perms) t->seeded_perm.alloc(B * N, s, false);
+  uint8_t* rho = d_out_factors ? (uint8_t*)d_out_factors : t->seeded_rho.p;
+  uint32_t* perm = d_out_perms ? (uint32_t*)d_out_perms : t->seeded_perm.p;
+  t->sample_dev(B, (const uint8_t*)d_seeds, (uint32_t)N, (uint32_t)N, rho, perm);
+  t->prove_dev(B, (const uint8_t*)d_decks, rho, perm, (const uint8_t*)d_seeds, (uint8_t*)d_out_decks, (uint8_t*)d_out_proofs,
+               (int32_t*)d_status, (const uint8_t*)d_keys);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_keygen_batch(mp_table* t, size_t K, const uint8_t* seeds, const uint8_t* fs_init, uint8_t* out_keys, uint8_t* out_secret_keys,
+                    uint8_t* out_proofs, int32_t* status) {
+  if (!t || !seeds || !out_keys || !out_secret_keys || !status || (fs_init && !out_proofs))
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_keygen_batch: null argument");
+  if (K < 1 || K > SAMPLE_MAX_LANES) return fail(MP_ERR_BAD_ARGUMENT, "mp_keygen_batch: 1 <= K <= 1 048 576");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->keygen_host(K, seeds, fs_init, out_keys, out_secret_keys, out_proofs, status);
   return MP_OK;
   MP_CATCH
 }

@@ -277,6 +277,15 @@ struct mp_table {
                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
   virtual void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                                    uint8_t* out_keys, int32_t* player_status, int32_t* table_status) = 0;
+  // secrets from seeds (kernels_sample.hpp, "mpshuffle secret stream v1"): L seeds -> S wire scalars and a permutation of length P each;
+  // sample_dev takes device pointers and is enqueued on the context's stream, sample_host host buffers.  keygen_host: sk = the stream's
+  // single scalar, pk = sk G, and with fs_init the Schnorr proof of key ownership under the prover seed seeds[k]
+  virtual void sample_dev(size_t L, const uint8_t* seeds, uint32_t S, uint32_t P, uint8_t* out_scalars, uint32_t* out_perms) = 0;
+  virtual void sample_host(size_t L, const uint8_t* seeds, uint32_t S, uint32_t P, uint8_t* out_scalars, uint32_t* out_perms) = 0;
+  virtual void keygen_host(size_t K, const uint8_t* seeds, const uint8_t* fs_init, uint8_t* out_keys, uint8_t* out_secret_keys,
+                           uint8_t* out_proofs, int32_t* status) = 0;
+  mp::DevBuf<uint8_t> seeded_rho;      // the sampled witnesses of mp_shuffle_and_remask_batch_seeded_dev: [B][N] wire scalars ...
+  mp::DevBuf<uint32_t> seeded_perm;    // ... and [B][N] indices; they stay here unless the caller asks for them
   // screening of the sigma verifiers (kernels_screen.hpp; mp_set_sigma_screen): lanes per group equation (0 = off), the smallest call screened
   virtual int set_sigma_screen(uint32_t lanes_per_group, size_t min_lanes) = 0;
   virtual void sigma_screen_stats(uint64_t out[4]) const = 0;

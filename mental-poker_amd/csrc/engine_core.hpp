@@ -7,6 +7,7 @@
 #include "kernels_sigma.hpp"
 #include "kernels_open.hpp"
 #include "kernels_deal.hpp"
+#include "kernels_sample.hpp"
 #include "kernels_screen.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
@@ -2562,6 +2563,8 @@ struct Table : mp_table {
     bool ready = false;
     Phase vph, pph1, pph2, sph;     // checks of the verifier | (x G, x pk) | the commitments (r G, r pk) | checks of the seating proofs
     PhaseDev vdev, pdev1, pdev2, sdev;
+    Phase kph1, kph2;               // key generation: pk = sk G | the commitment r G
+    PhaseDev kdev1, kdev2;
     uint32_t nJ = 0, nD = 0, nT = 0;
     uint32_t fs_seed[2][8];         // Blake2s("Masking Proof"), Blake2s("Remasking Proof")  [REF mod.rs:80-81]
     Workspace w;
@@ -2622,13 +2625,27 @@ struct Table : mp_table {
         pb.addend(sl.A, true);
         pb.end();
       }
+      {
+        PhaseBuilder pb(deal.kph1, np, FCHUNK, VCHUNK);
+        pb.begin(sl.a);
+        pb.fixed(sl.x, fb.G());
+        pb.end();
+        pb.normalize(sl.a, 1);
+      }
+      {
+        PhaseBuilder pb(deal.kph2, np, FCHUNK, VCHUNK);
+        pb.begin(sl.A);
+        pb.fixed(sl.r, fb.G());
+        pb.end();
+        pb.normalize(sl.A, 1);
+      }
       // x pk and r pk share the base: both phases know the window table of pk as table slot 0, and the first one builds it
       if (deal.pph1.tables.size() != 1 || deal.pph2.tables.size() != 1 || deal.pph1.tables[0].s != l.g + 1 || deal.pph2.tables[0].s != l.g + 1 ||
           deal.pph1.tables[0].b != 0 || deal.pph2.tables[0].b != 0)
         throw std::logic_error("deal plan: the phases do not share the table of pk");
       deal.pph2.tables.clear();
       deal.nJ = np;
-      for (const Phase* ph : {&deal.vph, &deal.pph1, &deal.pph2, &deal.sph}) {
+      for (const Phase* ph : {&deal.vph, &deal.pph1, &deal.pph2, &deal.sph, &deal.kph1, &deal.kph2}) {
         deal.nD = std::max(deal.nD, ph->n_dslots);
         deal.nT = std::max(deal.nT, ph->n_tslots);
       }
@@ -2636,6 +2653,8 @@ struct Table : mp_table {
       deal.pdev1.upload(deal.pph1, s);
       deal.pdev2.upload(deal.pph2, s);
       deal.sdev.upload(deal.sph, s);
+      deal.kdev1.upload(deal.kph1, s);
+      deal.kdev2.upload(deal.kph2, s);
       const char* names[2] = {"Masking Proof", "Remasking Proof"};
       for (int k = 0; k < 2; ++k) {
         Blake2sState st;
@@ -2795,6 +2814,65 @@ struct Table : mp_table {
     rt::d2h(out_keys, dout.p, (size_t)Tn * G_::PB, s);
     rt::d2h(player_status, dps.p, (size_t)B * 4, s);
     rt::d2h(table_status, dts.p, (size_t)Tn * 4, s);
+    rt::stream_sync(s);
+  }
+
+  // ---------------------------------------------------------------- secrets from seeds (kernels_sample.hpp)
+  // One lane per seed; nothing is allocated and nothing waits: a seeded prove call is this launch in front of prove_dev.
+  void sample_dev(size_t L, const uint8_t* seeds, uint32_t S, uint32_t P, uint8_t* out_scalars, uint32_t* out_perms) override {
+    SampleArgs a{seeds, out_scalars, out_perms, S, P};
+    MP_RUN(k_sample_secrets, C, (uint32_t)L, 1, a);
+  }
+  void sample_host(size_t L, const uint8_t* seeds, uint32_t S, uint32_t P, uint8_t* out_scalars, uint32_t* out_perms) override {
+    rt::Stream s = ctx->stream;
+    DevBuf<uint8_t> dseed, dsc;
+    DevBuf<uint32_t> dpm;
+    dseed.alloc(L * 32, s, false);
+    if (S) dsc.alloc(L * S * 32, s, false);
+    if (P) dpm.alloc(L * P, s, false);
+    rt::h2d(dseed.p, seeds, L * 32, s);
+    sample_dev(L, dseed.p, S, P, dsc.p, dpm.p);
+    if (S) rt::d2h(out_scalars, dsc.p, L * S * 32, s);
+    if (P) rt::d2h(out_perms, dpm.p, L * P * 4, s);
+    rt::stream_sync(s);
+  }
+  // Key generation [REF mod.rs:123-149]: the secret key goes from the sampler's output into the statement on the device; pk = sk G
+  // and the commitment r G come from the table's fixed-base table, the transcript is that of the seating lanes (one base).
+  void keygen_host(size_t K_, const uint8_t* seeds, const uint8_t* fs_init, uint8_t* out_keys, uint8_t* out_secret_keys, uint8_t* out_proofs,
+                   int32_t* status) override {
+    rt::Stream s = ctx->stream;
+    const uint32_t B = (uint32_t)K_;
+    const size_t psz = (size_t)G_::PB + 32;
+    deal_prepare(B);
+    Workspace& w = deal.w;
+    const SigmaLay l = seat_lay();
+    DevBuf<uint8_t> dseed, dsk, dpk, dpf;
+    dseed.alloc((size_t)B * 32, s, false); dsk.alloc((size_t)B * 32, s, false); dpk.alloc((size_t)B * G_::PB, s, false);
+    rt::h2d(dseed.p, seeds, (size_t)B * 32, s);
+    sample_dev(B, dseed.p, 1, 0, dsk.p, nullptr);
+    KeygenStmtArgs ka{w.P.p, fbpts.p, l.g, w.Bpad, FixedBases{n}.G()};
+    MP_RUN(k_keygen_stmt, C, B, 1, ka);
+    LoadScalarsArgs lx{dsk.p, w.S.p, w.status.p, w.Bpad, 1, l.x};
+    MP_RUN(k_load_scalars, C, B, 1, lx);
+    run_phase(deal.kdev1, w, B);
+    StorePointsArgs so{dpk.p, w.P.p, w.Bpad, 1, l.a};
+    MP_RUN(k_store_points, C, B, 1, so);
+    if (fs_init) {
+      dpf.alloc((size_t)B * psz, s, false);
+      rt::h2d(deal.fs.p, fs_init, (size_t)B * 32, s);
+      const FsDev f{w.stage.p, w.seed.p, w.Bpad};
+      SigmaInitArgs ia{w.S.p, dseed.p, l, w.Bpad, f, w.P.p, deal.fs.p};
+      MP_RUN(k_sigma_init, C, B, 1, ia);
+      run_phase(deal.kdev2, w, B);
+      SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 1};
+      MP_RUN(k_sigma_fs, C, B, 1, fa);
+      SigmaIoArgs io{dpf.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
+      MP_RUN(k_sigma_store, C, B, 2, io);
+      rt::d2h(out_proofs, dpf.p, (size_t)B * psz, s);
+    }
+    rt::d2h(out_keys, dpk.p, (size_t)B * G_::PB, s);
+    rt::d2h(out_secret_keys, dsk.p, (size_t)B * 32, s);
+    rt::d2h(status, w.status.p, (size_t)B * 4, s);
     rt::stream_sync(s);
   }
 

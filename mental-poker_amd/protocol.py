@@ -9,6 +9,7 @@ All computation happens in libmpshuffle.so (HIP, gfx950); this file only moves b
     PublicKey    64 bytes                                (el_gamal::PublicKey)
     ZKProofShuffle  bytes of length proof_size(m, n)     (shuffle::proof::Proof)
 """
+import hashlib
 import struct
 import threading
 
@@ -528,6 +529,59 @@ class DLCards:
         return [None if s == 0 else (CryptoError(self.engine.check_name(s)) if s > 0 else CardProtocolError.io(self.engine.check_name(s)))
                 for s in st]
 
+    # -- secrets drawn on the device from seeds ("mpshuffle secret stream v1", include/mpshuffle.h; secret_stream below is the CPU
+    #    statement): one fresh 32-byte CSPRNG seed per proof / per player, never reused; the seed is all a caller has to store
+    def _seed_bytes(self, seeds):
+        if not seeds or any(len(bytes(s)) != 32 for s in seeds):
+            raise CardProtocolError.io("at least one seed, 32 bytes each")
+        return b"".join(bytes(s) for s in seeds)
+
+    def sample_shuffle_witnesses(self, seeds, pp):
+        """[REF examples/round.rs:265-266] for many shuffles: -> (permutations, masking_factors), one Permutation and one list of m*n
+        scalars per seed -- what shuffle_and_remask_batch_seeded uses for the same seeds"""
+        N = pp.m * pp.n
+        try:
+            sc, pm = self._t(pp).sample_secrets_batch(self._seed_bytes(seeds), N, N)
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        perms = [Permutation(pm[b * N:(b + 1) * N]) for b in range(len(seeds))]
+        return perms, [[int.from_bytes(sc[(b * N + i) * 32:(b * N + i + 1) * 32], "little") for i in range(N)] for b in range(len(seeds))]
+
+    def shuffle_and_remask_batch_seeded(self, seeds, pp, shared_key_or_keys, decks):
+        """shuffle_and_remask_batch with the witness of proof b drawn on the device from seeds[b], which is also its prover seed;
+        shared_key_or_keys: one aggregate key for all proofs, or a list of one key per proof -> per proof (deck, proof) or the
+        CardProtocolError of its lane"""
+        one = isinstance(shared_key_or_keys, (bytes, bytearray, memoryview))
+        keys = None if one else [bytes(k) for k in shared_key_or_keys]
+        if len(decks) != len(seeds) or (keys is not None and len(keys) != len(seeds)):
+            raise CardProtocolError.io("one deck (and one key, if keys are given per proof) per seed")
+        t = self.table(pp, bytes(shared_key_or_keys) if one else keys[0])
+        try:
+            d, p, st = t.shuffle_and_remask_batch_seeded(b"".join(b"".join(dk) for dk in decks), self._seed_bytes(seeds),
+                                                         None if one else b"".join(keys))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        N, ps, cb = pp.m * pp.n, t.proof_bytes, 2 * self.engine.point_bytes
+        return [CardProtocolError.io(self.engine.check_name(s)) if s < 0 else
+                ([d[(b * N + i) * cb:(b * N + i + 1) * cb] for i in range(N)], p[b * ps:(b + 1) * ps]) for b, s in enumerate(st)]
+
+    def player_keygen_batch(self, seeds, pp, infos=None):
+        """player_keygen [REF mod.rs:123-130] for many players: sk = the stream's single scalar, pk = sk G -> [(pk, sk)]; with infos (one
+        player_public_info per seed) also prove_key_ownership under the prover seed seeds[k] -> [(pk, sk, ZKProofKeyOwnership)]"""
+        if infos is not None and len(infos) != len(seeds):
+            raise CardProtocolError.io("one player_public_info per seed")
+        fs = None if infos is None else b"".join(self.engine.blake2s(KEY_OWN_RNG_SEED + bytes(i)) for i in infos)
+        try:
+            pk, sk, prf, st = self._t(pp).keygen_batch(self._seed_bytes(seeds), fs)
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        bad = [v for v in st if v != 0]
+        if bad:
+            raise CardProtocolError.io(self.engine.check_name(bad[0]))
+        pb, psz = self.engine.point_bytes, self.engine.point_bytes + 32
+        rows = [(pk[k * pb:(k + 1) * pb], int.from_bytes(sk[k * 32:(k + 1) * 32], "little")) for k in range(len(seeds))]
+        return rows if prf is None else [r + (prf[k * psz:(k + 1) * psz],) for k, r in enumerate(rows)]
+
     def verify_shuffle_batch(self, pp, shared_key, original_decks, shuffled_decks, proofs):
         t = self.table(pp, shared_key)
         try:
@@ -606,3 +660,16 @@ class ChaCha20Rng:
             self.counter += 1
         lo, hi = self.buf.pop(0), self.buf.pop(0)
         return lo | (hi << 32)
+
+
+SECRET_STREAM_TAG = b"mpshuffle secret stream v1"
+
+
+def secret_stream(curve, seed, S, P):
+    """the CPU statement of "mpshuffle secret stream v1" (include/mpshuffle.h): S scalars, then a permutation of length P, from
+    ChaCha20Rng(BLAKE2s(tag || seed)) -> (list of S ints in [0, q), list of P indices with out[i] = in[perm[i]])"""
+    if len(bytes(seed)) != 32:
+        raise CardProtocolError.io("the seed is 32 bytes")
+    rng = ChaCha20Rng(hashlib.blake2s(SECRET_STREAM_TAG + bytes(seed)).digest())
+    scalars = [fr_rand(curve, rng) for _ in range(S)]
+    return scalars, Permutation.new(rng, P).mapping
