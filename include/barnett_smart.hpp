@@ -50,9 +50,18 @@ class DLCardsT {
     if (mp_point_size(curve_id) != PB) throw CardProtocolError("curve / point size mismatch");
     if (mp_ctx_create(curve_id, device, &ctx_) != MP_OK) throw CardProtocolError(mp_last_error());
   }
+  // The same over a device pool (mpshuffle.h "device pool"): devices[i] is the device of member i, a device named several times gives
+  // lanes on it.  shuffle_and_remask_batch / verify_shuffle_batch cut their proofs into blocks over the members -- same bytes, same
+  // status words --, every other member runs on member 0.
+  DLCardsT(int curve_id, const std::vector<int>& devices) : curve_(curve_id) {
+    if (mp_point_size(curve_id) != PB) throw CardProtocolError("curve / point size mismatch");
+    if (mp_pool_create(curve_id, devices.size(), devices.data(), &pool_) != MP_OK) throw CardProtocolError(mp_last_error());
+    ctx_ = mp_pool_member_ctx(pool_, 0);
+  }
   ~DLCardsT() {
-    if (table_) mp_table_destroy(table_);
-    mp_ctx_destroy(ctx_);
+    unbind();
+    if (pool_) mp_pool_destroy(pool_);      // (its contexts go with it)
+    else mp_ctx_destroy(ctx_);
   }
   DLCardsT(const DLCardsT&) = delete;
   DLCardsT& operator=(const DLCardsT&) = delete;
@@ -275,7 +284,68 @@ class DLCardsT {
     return p;
   }
 
+  // shuffle_and_remask / verify_shuffle for many decks under one aggregate key (mp_*_batch; through the pool when there is one).
+  // Status words are returned, not thrown: 0, the code of the first failing check (mp_check_name), or < 0.
+  struct Shuffles {
+    std::vector<std::vector<MaskedCard>> decks;
+    std::vector<ZKProofShuffle> proofs;
+    std::vector<int32_t> status;
+  };
+  Shuffles shuffle_and_remask_batch(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const PublicKey& shared_key,
+                                    const std::vector<std::vector<MaskedCard>>& decks, const std::vector<std::vector<Scalar>>& masking_factors,
+                                    const std::vector<Permutation>& permutations) {
+    const size_t N = (size_t)pp.m * pp.n, B = rng_seeds.size();
+    if (!B || decks.size() != B || masking_factors.size() != B || permutations.size() != B)
+      throw CardProtocolError("shuffle_and_remask_batch: one deck, one factor list and one permutation per seed, at least one");
+    std::vector<MaskedCard> in(B * N), out(B * N);
+    std::vector<Scalar> rho(B * N);
+    std::vector<uint32_t> perm(B * N);
+    for (size_t b = 0; b < B; ++b) {
+      if (decks[b].size() != N || masking_factors[b].size() != N || permutations[b].mapping.size() != N)
+        throw CardProtocolError("deck, masking factors and permutation must have m*n entries");
+      std::copy(decks[b].begin(), decks[b].end(), in.begin() + b * N);
+      std::copy(masking_factors[b].begin(), masking_factors[b].end(), rho.begin() + b * N);
+      std::copy(permutations[b].mapping.begin(), permutations[b].mapping.end(), perm.begin() + b * N);
+    }
+    bind(pp, shared_key);
+    const size_t psz = mp_proof_size_curve(curve_, pp.m, pp.n);
+    std::vector<uint8_t> proofs(B * psz);
+    Shuffles r{std::vector<std::vector<MaskedCard>>(B), std::vector<ZKProofShuffle>(B), std::vector<int32_t>(B)};
+    const int rc = ptable_ ? mp_pool_shuffle_and_remask_batch(ptable_, B, nullptr, in[0].data(), rho[0].data(), perm.data(), rng_seeds[0].data(),
+                                                              out[0].data(), proofs.data(), r.status.data())
+                           : mp_shuffle_and_remask_batch(table_, B, in[0].data(), rho[0].data(), perm.data(), rng_seeds[0].data(), out[0].data(),
+                                                         proofs.data(), r.status.data());
+    if (rc != MP_OK) throw CardProtocolError(mp_last_error());
+    for (size_t b = 0; b < B; ++b) {
+      r.decks[b].assign(out.begin() + b * N, out.begin() + (b + 1) * N);
+      r.proofs[b].assign(proofs.begin() + b * psz, proofs.begin() + (b + 1) * psz);
+    }
+    return r;
+  }
+  std::vector<int32_t> verify_shuffle_batch(const Parameters& pp, const PublicKey& shared_key, const std::vector<std::vector<MaskedCard>>& original_decks,
+                                            const std::vector<std::vector<MaskedCard>>& shuffled_decks, const std::vector<ZKProofShuffle>& proofs) {
+    const size_t N = (size_t)pp.m * pp.n, B = proofs.size(), psz = mp_proof_size_curve(curve_, pp.m, pp.n);
+    if (!B || original_decks.size() != B || shuffled_decks.size() != B)
+      throw CardProtocolError("verify_shuffle_batch: one deck and one shuffled deck per proof, at least one");
+    std::vector<MaskedCard> in(B * N), shuf(B * N);
+    std::vector<uint8_t> pf(B * psz);
+    for (size_t b = 0; b < B; ++b) {
+      if (original_decks[b].size() != N || shuffled_decks[b].size() != N || proofs[b].size() != psz)
+        throw CardProtocolError("decks must have m*n entries and proofs their wire length");
+      std::copy(original_decks[b].begin(), original_decks[b].end(), in.begin() + b * N);
+      std::copy(shuffled_decks[b].begin(), shuffled_decks[b].end(), shuf.begin() + b * N);
+      std::copy(proofs[b].begin(), proofs[b].end(), pf.begin() + b * psz);
+    }
+    bind(pp, shared_key);
+    std::vector<int32_t> status(B);
+    const int rc = ptable_ ? mp_pool_verify_shuffle_batch(ptable_, B, nullptr, in[0].data(), shuf[0].data(), pf.data(), status.data())
+                           : mp_verify_shuffle_batch(table_, B, in[0].data(), shuf[0].data(), pf.data(), status.data());
+    if (rc != MP_OK) throw CardProtocolError(mp_last_error());
+    return status;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
+  mp_pool_table* pool_table() const { return ptable_; }      // NULL without a device list
 
  private:
   DealtCards mask_batch(int kind, const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const std::vector<PublicKey>& shared_keys,
@@ -314,14 +384,26 @@ class DLCardsT {
   }
   void bind(const Parameters& pp, const PublicKey& pk) {
     if (table_ && pp.raw == bound_params_ && pk == bound_pk_ && pp.m == bound_m_) return;
-    if (table_) mp_table_destroy(table_);
-    table_ = nullptr;
-    if (mp_table_create(ctx_, pp.m, pp.n, pp.raw.data(), pk.data(), &table_) != MP_OK) throw CardProtocolError(mp_last_error());
+    unbind();
+    if (pool_) {      // member 0's table is borrowed from the pool table
+      if (mp_pool_table_create(pool_, pp.m, pp.n, pp.raw.data(), pk.data(), 0, &ptable_) != MP_OK) throw CardProtocolError(mp_last_error());
+      table_ = mp_pool_table_member(ptable_, 0);
+    } else if (mp_table_create(ctx_, pp.m, pp.n, pp.raw.data(), pk.data(), &table_) != MP_OK) {
+      throw CardProtocolError(mp_last_error());
+    }
     bound_params_ = pp.raw;
     bound_pk_ = pk;
     bound_m_ = pp.m;
   }
+  void unbind() {
+    if (ptable_) mp_pool_table_destroy(ptable_);
+    else if (table_) mp_table_destroy(table_);
+    ptable_ = nullptr;
+    table_ = nullptr;
+  }
   int curve_;
+  mp_pool* pool_ = nullptr;             // device-list constructor: ctx_ and table_ are member 0's, borrowed
+  mp_pool_table* ptable_ = nullptr;
   mp_ctx* ctx_ = nullptr;
   mp_table* table_ = nullptr;
   std::vector<uint8_t> bound_params_;

@@ -363,6 +363,58 @@ int mp_set_toom_cook(mp_table* t, int on);
  * arkworks with checks) may switch it off -- it costs about three verifications per proof.  No effect on prime-order curves. */
 int mp_set_subgroup_check(mp_table* t, int on);
 
+/* ---- device pool: several contexts -- lanes of one GPU, or several GPUs -- behind one handle -----------------------------------------
+ * The per-player proofs of a round are independent [REF examples/round.rs:263-350] and deterministic in their seeds, and contexts share
+ * nothing, so a batch can be cut into contiguous blocks that run on several contexts at once.  A pool is `n_members` members; a member is
+ * one mp_ctx on one device plus one persistent worker thread.  devices[i] is the device of member i; a device may appear several times --
+ * those members are lanes that run side by side on that chip (batches that do not fill it alone) --, members on different devices are the
+ * multi-GPU case; devices == NULL: member i runs on device i.  mp_ctx_create is the one-member case and stays what a caller with one
+ * context per process uses.  n_members of 0 or above 64: MP_ERR_BAD_ARGUMENT; a device index that does not exist: MP_ERR_NO_DEVICE; either
+ * way nothing is left allocated and mp_last_error names the member.  mp_pool_member_ctx: the context of member i, borrowed (NULL if there is
+ * none): never to mp_ctx_destroy.  mp_pool_destroy: after every pool table of the pool has been destroyed and no call is in flight.
+ * mp_pool_table_create: one mp_table per member from the one host copy of the parameters (shared_key NULL: keyless tables, as
+ * mp_table_create_params).  The first member of every distinct device builds the fixed-base window tables -- the devices build at once,
+ * each on its member's worker; tables are recomputed per GPU, nothing is copied between devices --, the further
+ * members of that device build nothing and hold no second copy: they read the first member's tables (27-48 GB per table at the widest
+ * windows).  fb_window_bits as mp_table_create_ex; 0 chooses the width once per device.  A build that fails on any member fails the call
+ * with that member's code (the lowest member's, if several), mp_last_error names it, and the other members' tables are released.
+ * mp_pool_table_member: the table of member i, BORROWED: valid until mp_pool_table_destroy, never to be passed to mp_table_destroy.  Settings
+ * (mp_set_group_verify, mp_set_validated, mp_set_io_chunk, ...) are made per member through it -- the pool has no setter of its own but
+ * mp_pool_set_min_shard --, and a device-resident caller shards its own batches over the members with the _dev entry points.
+ * mp_pool_shuffle_and_remask_batch / mp_pool_verify_shuffle_batch: host buffers in the layout of mp_*_batch_keys; shared_keys NULL = the
+ * table's own key (mp_*_batch).  The proofs [0, B) are cut into K contiguous blocks -- base, rem = divmod(B, K), the first rem blocks hold
+ * one more -- for the first K = min(members, max(1, B / min_shard)) members (mp_pool_set_min_shard: proofs a block must hold before the call
+ * takes another member, default 1); every worker runs the single-table call on its slice of every buffer and the caller's thread waits for
+ * all of them.  Outputs and status[b] are byte for byte those of the same call on one mp_table.  Invalid arguments (null pointers, a keyless
+ * table without shared_keys, B = 0) give the single-table call's return value, before anything is dispatched.  If a member's call fails as a
+ * whole (< 0) the pool call returns the code of the lowest such member and mp_last_error, on the calling thread, its text behind "member i
+ * (device d): "; the other members' blocks are complete.
+ * Threads: pool calls from several host threads are safe and run one after the other (the pool's lock; the stats getters take it too);
+ * calls made meanwhile on a borrowed member table from another thread are safe as well and take their turn through that context's lock.
+ * mp_pool_stats: out[0] pool calls, [1] proofs, [2] members the last call used, [3] fixed-base table builds performed (= distinct devices),
+ * [4] members, [5..7] reserved (0).  mp_pool_member_stats: out[0] device, [1] calls that gave member i a block, [2] its proofs, [3] its busy
+ * time in microseconds (host clock around the member's calls).
+ * Not offered through the pool: chain verification (its link-major layout needs a strided gather), the seeded prover, the sigma, deal and
+ * open calls, device-resident pool calls (shard over mp_pool_table_member), and any collective: the library does not use RCCL. */
+typedef struct mp_pool mp_pool;
+typedef struct mp_pool_table mp_pool_table;
+int mp_pool_create(int curve_id, size_t n_members, const int* devices, mp_pool** out);
+void mp_pool_destroy(mp_pool* p);
+size_t mp_pool_size(const mp_pool* p);
+mp_ctx* mp_pool_member_ctx(mp_pool* p, size_t i);
+int mp_pool_table_create(mp_pool* p, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key, uint32_t fb_window_bits,
+                         mp_pool_table** out);
+void mp_pool_table_destroy(mp_pool_table* pt);
+mp_table* mp_pool_table_member(mp_pool_table* pt, size_t i);
+int mp_pool_set_min_shard(mp_pool_table* pt, size_t proofs);
+int mp_pool_shuffle_and_remask_batch(mp_pool_table* pt, size_t B, const uint8_t* shared_keys, const uint8_t* decks,
+                                     const uint8_t* masking_factors, const uint32_t* permutations, const uint8_t* prover_seeds,
+                                     uint8_t* out_decks, uint8_t* out_proofs, int32_t* status);
+int mp_pool_verify_shuffle_batch(mp_pool_table* pt, size_t B, const uint8_t* shared_keys, const uint8_t* decks, const uint8_t* shuffled_decks,
+                                 const uint8_t* proofs, int32_t* status);
+int mp_pool_stats(const mp_pool_table* pt, uint64_t out[8]);
+int mp_pool_member_stats(const mp_pool_table* pt, size_t i, uint64_t out[4]);
+
 /* ---- building blocks (host buffers) ------------------------------------------------------------------------
  * mp_remask_batch: out[i] = in[i] + (rho_i * G, rho_i * pk)        [REF remasking.rs:16-18]
  * mp_msm:          n_msm independent variable-base MSMs of k terms: out[j] = sum_t scalars[j][t] * points[j][t]

@@ -6,6 +6,7 @@ and `Engine(...)` raises `NoDeviceError` if no MI355X is visible.
 import ctypes
 import os
 import subprocess
+import weakref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmpshuffle.so")
@@ -29,6 +30,9 @@ SYMBOLS = [
     "mp_set_sigma_screen", "mp_sigma_screen_stats",
     "mp_sample_secrets_batch", "mp_sample_secrets_batch_dev", "mp_shuffle_and_remask_batch_seeded", "mp_shuffle_and_remask_batch_seeded_dev",
     "mp_keygen_batch",
+    "mp_pool_create", "mp_pool_destroy", "mp_pool_size", "mp_pool_member_ctx", "mp_pool_table_create", "mp_pool_table_destroy",
+    "mp_pool_table_member", "mp_pool_set_min_shard", "mp_pool_shuffle_and_remask_batch", "mp_pool_verify_shuffle_batch", "mp_pool_stats",
+    "mp_pool_member_stats",
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
@@ -263,6 +267,23 @@ def bind(cdll):
     cdll.mp_shuffle_and_remask_batch_seeded_dev.argtypes = [c.c_void_p, c.c_size_t] + [c.c_void_p] * 8
     cdll.mp_keygen_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, u8p, u8p, i32p]
     cdll.mp_sigma_screen_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
+    cdll.mp_pool_create.argtypes = [c.c_int, c.c_size_t, c.POINTER(c.c_int), c.POINTER(c.c_void_p)]
+    cdll.mp_pool_destroy.argtypes = [c.c_void_p]
+    cdll.mp_pool_destroy.restype = None
+    cdll.mp_pool_size.argtypes = [c.c_void_p]
+    cdll.mp_pool_size.restype = c.c_size_t
+    cdll.mp_pool_member_ctx.argtypes = [c.c_void_p, c.c_size_t]
+    cdll.mp_pool_member_ctx.restype = c.c_void_p
+    cdll.mp_pool_table_create.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, u8p, u8p, c.c_uint32, c.POINTER(c.c_void_p)]
+    cdll.mp_pool_table_destroy.argtypes = [c.c_void_p]
+    cdll.mp_pool_table_destroy.restype = None
+    cdll.mp_pool_table_member.argtypes = [c.c_void_p, c.c_size_t]
+    cdll.mp_pool_table_member.restype = c.c_void_p
+    cdll.mp_pool_set_min_shard.argtypes = [c.c_void_p, c.c_size_t]
+    cdll.mp_pool_shuffle_and_remask_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_pool_verify_shuffle_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, u8p, u8p, i32p]
+    cdll.mp_pool_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
+    cdll.mp_pool_member_stats.argtypes = [c.c_void_p, c.c_size_t, c.POINTER(c.c_uint64)]
     for fn, at in (("mp_serialized_point_size", [c.c_int]), ("mp_serialized_deck_size", [c.c_int, c.c_size_t]),
                    ("mp_serialized_params_size", [c.c_int, c.c_uint32]), ("mp_serialized_proof_size", [c.c_int, c.c_uint32, c.c_uint32])):
         getattr(cdll, fn).argtypes = at
@@ -387,9 +408,18 @@ class Engine:
         self.h = h
         self.point_bytes = self.lib.mp_point_size(CURVE_IDS[curve])     # 64; 96 on bls12_377
 
+    @classmethod
+    def borrowed(cls, curve, h, lib):
+        """the context of a pool member (Pool.engine): the pool owns it, close() only forgets the handle"""
+        self = cls.__new__(cls)
+        self.lib, self.curve, self.h, self._borrowed = lib, curve, ctypes.c_void_p(h), True
+        self.point_bytes = lib.mp_point_size(CURVE_IDS[curve])
+        return self
+
     def close(self):
         if getattr(self, "h", None):
-            self.lib.mp_ctx_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                self.lib.mp_ctx_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -493,9 +523,22 @@ class Table:
         self.fb_bits = self.lib.mp_table_window_bits(h)      # (fb_bits = 0: the engine chose by free HBM, as mp_table_create does)
         self.proof_bytes = eng.proof_size(m, n)
 
+    @classmethod
+    def borrowed(cls, eng, h, m, n, params, shared_key):
+        """the table of a pool member (PoolTable.member): the pool table owns it, close() only forgets the handle"""
+        self = cls.__new__(cls)
+        self.eng, self.lib, self.m, self.n, self.N = eng, eng.lib, m, n, m * n
+        self.params, self.shared_key = params, shared_key
+        self.pb, self.cb = eng.point_bytes, 2 * eng.point_bytes
+        self.h, self._borrowed = ctypes.c_void_p(h), True
+        self.fb_bits = self.lib.mp_table_window_bits(self.h)
+        self.proof_bytes = eng.proof_size(m, n)
+        return self
+
     def close(self):
         if getattr(self, "h", None):
-            self.lib.mp_table_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                self.lib.mp_table_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -974,3 +1017,138 @@ class Table:
         v = [ctypes.c_uint64() for _ in range(4)]
         self.eng._chk(self.lib.mp_work_census(self.h, *[ctypes.byref(x) for x in v]))
         return dict(prove_terms=v[0].value, verify_terms=v[1].value, prove_point_ops=v[2].value, verify_point_ops=v[3].value)
+
+
+class Pool:
+    """one mp_pool: contexts behind one handle (include/mpshuffle.h, "device pool").  devices[i] is the device of member i; a device named
+    several times gives lanes that run side by side on it; an int k means devices 0 .. k-1"""
+
+    def __init__(self, curve="stark", devices=(0,), lib=None):
+        self.lib = lib if lib is not None else load()
+        self.curve = curve
+        self.devices = list(range(devices)) if isinstance(devices, int) else [int(d) for d in devices]
+        n = len(self.devices)
+        h = ctypes.c_void_p()
+        rc = self.lib.mp_pool_create(CURVE_IDS[curve], n, (ctypes.c_int * max(n, 1))(*self.devices), ctypes.byref(h))
+        if rc != 0:
+            text = self.lib.mp_last_error().decode()
+            raise (NoDeviceError if rc == MP_ERR_NO_DEVICE else NativeError)(rc, text)
+        self.h = h
+        self.point_bytes = self.lib.mp_point_size(CURVE_IDS[curve])
+        self._tables = weakref.WeakSet()      # the pool's tables must go before it: close() closes those still open
+
+    def __len__(self):
+        return self.lib.mp_pool_size(self.h)
+
+    def engine(self, i=0):
+        """member i's context as a non-owning Engine"""
+        h = self.lib.mp_pool_member_ctx(self.h, i)
+        if not h:
+            raise NativeError(MP_ERR_BAD_ARGUMENT, "pool has no member %d" % i)
+        return Engine.borrowed(self.curve, h, self.lib)
+
+    def table(self, m, n, params, shared_key=None, fb_bits=8):
+        """shared_key None: a keyless pool table (one aggregate key per proof)"""
+        return PoolTable(self, m, n, params, shared_key, fb_bits)
+
+    def close(self):
+        if getattr(self, "h", None):
+            for t in list(self._tables):
+                t.close()
+            self.lib.mp_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PoolTable:
+    """one mp_pool_table: a Table per pool member; the members of one device share its fixed-base tables.  The batch calls cut their
+    proofs into contiguous blocks over the members and return the bytes and status words of the same call on one Table"""
+
+    def __init__(self, pool, m, n, params, shared_key=None, fb_bits=8):
+        self.pool, self.lib, self.m, self.n, self.N = pool, pool.lib, m, n, m * n
+        self.params, self.shared_key = bytes(params), (bytes(shared_key) if shared_key is not None else None)
+        self.pb, self.cb = pool.point_bytes, 2 * pool.point_bytes
+        if len(self.params) != self.pb * (n + 3) or (self.shared_key is not None and len(self.shared_key) != self.pb):
+            raise NativeError(MP_ERR_BAD_ARGUMENT, "parameters / shared key have the wrong length")
+        h = ctypes.c_void_p()
+        self._chk(self.lib.mp_pool_table_create(pool.h, m, n, _in(self.params), _in(self.shared_key) if self.shared_key is not None else None,
+                                                fb_bits, ctypes.byref(h)))
+        self.h = h
+        pool._tables.add(self)
+        self.proof_bytes = self.lib.mp_proof_size_curve(CURVE_IDS[pool.curve], m, n)
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise NativeError(rc, self.lib.mp_last_error().decode())
+        return rc
+
+    _need = Table._need
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mp_pool_table_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def member(self, i):
+        """member i's table as a non-owning Table: settings, direct calls, device-resident callers that shard themselves"""
+        h = self.lib.mp_pool_table_member(self.h, i)
+        if not h:
+            raise NativeError(MP_ERR_BAD_ARGUMENT, "pool table has no member %d" % i)
+        return Table.borrowed(self.pool.engine(i), h, self.m, self.n, self.params, self.shared_key)
+
+    def set_min_shard(self, proofs):
+        """proofs a block must hold before a call takes another member (default 1)"""
+        self._chk(self.lib.mp_pool_set_min_shard(self.h, int(proofs)))
+
+    def stats(self):
+        """[pool calls, proofs, members used by the last call, fixed-base table builds (= distinct devices), members, 0, 0, 0]"""
+        v = (ctypes.c_uint64 * 8)()
+        self._chk(self.lib.mp_pool_stats(self.h, v))
+        return [int(x) for x in v]
+
+    def member_stats(self, i):
+        v = (ctypes.c_uint64 * 4)()
+        self._chk(self.lib.mp_pool_member_stats(self.h, i, v))
+        return dict(zip(["device", "calls", "proofs", "busy_us"], [int(x) for x in v]))
+
+    def shuffle_and_remask_batch(self, decks, factors, perms, seeds, keys=None):
+        """B proofs as Table.shuffle_and_remask_batch (keys: B wire points, one aggregate key per proof) -> (decks, proofs, status)"""
+        B = len(seeds) // 32
+        N = self.N
+        self._need("prover seeds", len(seeds), B * 32)
+        if keys is not None:
+            self._need("keys", len(keys), B * self.pb)
+        self._need("decks", len(decks), B * N * self.cb)
+        self._need("masking factors", len(factors), B * N * 32)
+        self._need("permutations", len(perms), B * N)
+        out_d = (ctypes.c_uint8 * max(B * N * self.cb, 1))()
+        out_p = (ctypes.c_uint8 * max(B * self.proof_bytes, 1))()
+        st = (ctypes.c_int32 * max(B, 1))()
+        pm = (ctypes.c_uint32 * max(B * N, 1))(*perms)
+        self._chk(self.lib.mp_pool_shuffle_and_remask_batch(self.h, B, _in(keys) if keys is not None else None, _in(decks), _in(factors), pm,
+                                                            _in(seeds), out_d, out_p, st))
+        return bytes(out_d)[:B * N * self.cb], bytes(out_p)[:B * self.proof_bytes], list(st)[:B]
+
+    def verify_shuffle_batch(self, decks, shuffled, proofs, keys=None):
+        N = self.N
+        B = len(decks) // (N * self.cb)
+        self._need("decks", len(decks), B * N * self.cb)
+        if keys is not None:
+            self._need("keys", len(keys), B * self.pb)
+        self._need("shuffled decks", len(shuffled), len(decks))
+        self._need("proofs", len(proofs), B * self.proof_bytes)
+        st = (ctypes.c_int32 * max(B, 1))()
+        self._chk(self.lib.mp_pool_verify_shuffle_batch(self.h, B, _in(keys) if keys is not None else None, _in(decks), _in(shuffled),
+                                                        _in(proofs), st))
+        return list(st)[:B]

@@ -6,6 +6,7 @@
 
 #include "engine_base.hpp"
 #include "coalesce.hpp"
+#include "pool.hpp"
 
 namespace mp {
 std::string& last_error() {
@@ -192,22 +193,25 @@ static uint32_t auto_window_bits(int curve, uint32_t n) {
 int mp_table_create(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key, mp_table** out) {
   return mp_table_create_ex(ctx, m, n, params, shared_key, 0, out);
 }
-int mp_table_create_ex(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key,
-                       uint32_t fb_window_bits, mp_table** out) {
+// fb_from: a table of the same parameters and key on the same device whose fixed-base tables the new one reads instead of building its
+// own (the lanes of a pool, pool.hpp); it takes that table's window width
+static int table_create(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key, uint32_t fb_window_bits,
+                        const mp_table* fb_from, mp_table** out) {
   if (!ctx || !params || !shared_key || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_table_create: null pointer");
   if (m < 2 || n < 2 || (uint64_t)m * n > 4096) return fail(MP_ERR_BAD_ARGUMENT, "mp_table_create: need m >= 2, n >= 2, m*n <= 4096");
   MP_TRY
   MP_ENTER(ctx);
+  if (fb_from) fb_window_bits = fb_from->fb_bits;
   const bool auto_bits = fb_window_bits == 0;
   if (auto_bits) fb_window_bits = auto_window_bits(ctx->curve, n);
   int rc = MP_OK;
   mp_table* t = nullptr;
   auto make = [&](uint32_t bits) {
     switch (ctx->curve) {
-      case 0: return make_table_Stark(ctx, m, n, params, shared_key, bits, &rc);
-      case 1: return make_table_Bn254(ctx, m, n, params, shared_key, bits, &rc);
-      case 3: return make_table_Bls12_377(ctx, m, n, params, shared_key, bits, &rc);
-      default: return make_table_Secp256k1(ctx, m, n, params, shared_key, bits, &rc);
+      case 0: return make_table_Stark(ctx, m, n, params, shared_key, bits, &rc, fb_from);
+      case 1: return make_table_Bn254(ctx, m, n, params, shared_key, bits, &rc, fb_from);
+      case 3: return make_table_Bls12_377(ctx, m, n, params, shared_key, bits, &rc, fb_from);
+      default: return make_table_Secp256k1(ctx, m, n, params, shared_key, bits, &rc, fb_from);
     }
   };
   if (!auto_bits) {
@@ -236,6 +240,10 @@ int mp_table_create_ex(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* param
   *out = t;
   return MP_OK;
   MP_CATCH
+}
+int mp_table_create_ex(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key,
+                       uint32_t fb_window_bits, mp_table** out) {
+  return table_create(ctx, m, n, params, shared_key, fb_window_bits, nullptr, out);
 }
 int mp_table_create_params(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, uint32_t fb_window_bits, mp_table** out) {
   // a table of the shared parameters only, for keyed batches: the enc generator G stands in for the (unused) fixed key
@@ -772,15 +780,29 @@ static void io_events(mp_io_stage& st) {
   }
 }
 
+// the call-level argument checks of the host-buffer batch calls: 0, or the code the call returns (the pool's calls decide by the same
+// checks before anything is dispatched)
+static int prove_batch_args(const mp_table* t, size_t B, const uint8_t* keys, const uint8_t* decks, const uint8_t* masking_factors,
+                            const uint32_t* permutations, const uint8_t* prover_seeds, const uint8_t* out_decks, const uint8_t* out_proofs,
+                            const int32_t* status, bool seeded = false) {
+  if (!t || !B || !decks || (!seeded && (!masking_factors || !permutations)) || !prover_seeds || !out_decks || !out_proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch: bad argument");
+  if (t->keyless && !keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: use the _keys entry points");
+  return 0;
+}
+static int verify_batch_args(const mp_table* t, size_t B, const uint8_t* keys, const uint8_t* decks, const uint8_t* shuffled_decks,
+                             const uint8_t* proofs, const int32_t* status) {
+  if (!t || !B || !decks || !shuffled_decks || !proofs || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_batch: bad argument");
+  if (t->keyless && !keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: use the _keys entry points");
+  return 0;
+}
 // seeded (mp_shuffle_and_remask_batch_seeded): no witness comes from the host -- every chunk's masking factors and permutations are sampled
 // from its prover seeds into the staging buffers the unseeded call uploads them to, and go back to the host only if asked for
 static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const uint8_t* decks, const uint8_t* masking_factors,
                             const uint32_t* permutations, const uint8_t* prover_seeds, uint8_t* out_decks,
                             uint8_t* out_proofs, int32_t* status, bool seeded = false, uint32_t* out_perms = nullptr,
                             uint8_t* out_factors = nullptr) {
-  if (!t || !B || !decks || (!seeded && (!masking_factors || !permutations)) || !prover_seeds || !out_decks || !out_proofs || !status)
-    return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch: bad argument");
-  if (t->keyless && !keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: use the _keys entry points");
+  if (int bad = prove_batch_args(t, B, keys, decks, masking_factors, permutations, prover_seeds, out_decks, out_proofs, status, seeded)) return bad;
   MP_TRY
   MP_ENTER(t->ctx);
   rt::Stream s = t->ctx->stream, up = t->ctx->h2d, down = t->ctx->d2h;
@@ -837,8 +859,7 @@ static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const ui
 }
 static int verify_batch_host(mp_table* t, size_t B, const uint8_t* keys, const uint8_t* decks, const uint8_t* shuffled_decks,
                              const uint8_t* proofs, int32_t* status) {
-  if (!t || !B || !decks || !shuffled_decks || !proofs || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_batch: bad argument");
-  if (t->keyless && !keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: use the _keys entry points");
+  if (int bad = verify_batch_args(t, B, keys, decks, shuffled_decks, proofs, status)) return bad;
   MP_TRY
   MP_ENTER(t->ctx);
   NoPipeline nopipe(t);
@@ -1003,6 +1024,140 @@ int mp_coalesce_stats(const mp_table* t, uint64_t out[8]) {
     v[5] += q.rerun;
     v[6] += q.wait_us;
   }
+  memcpy(out, v, sizeof(v));
+  return MP_OK;
+}
+
+// ---- the device pool (pool.hpp): contexts on one or several devices behind one handle; batches are cut into contiguous blocks
+int mp_pool_create(int curve_id, size_t n_members, const int* devices, mp_pool** out) {
+  if (!out) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_create: null out pointer");
+  if (curve_id < 0 || curve_id > 3) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_create: unknown curve id");
+  if (n_members == 0 || n_members > 64) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_create: 1 .. 64 members");
+  MP_TRY
+  std::unique_ptr<mp_pool> p(new mp_pool());      // (its destructor gives back whatever was created when a later member fails)
+  p->curve = curve_id;
+  p->members.resize(n_members);
+  for (size_t i = 0; i < n_members; ++i) {
+    mp_pool::Member& mb = p->members[i];
+    mb.device = devices ? devices[i] : (int)i;
+    const int rc = mp_ctx_create(curve_id, mb.device, &mb.ctx);
+    if (rc != MP_OK) return fail(rc, "mp_pool_create: " + pool_member_text(p.get(), i, last_error()));
+    mb.worker.reset(new PoolWorker());
+  }
+  *out = p.release();
+  return MP_OK;
+  MP_CATCH
+}
+void mp_pool_destroy(mp_pool* p) { delete p; }
+size_t mp_pool_size(const mp_pool* p) { return p ? p->members.size() : 0; }
+mp_ctx* mp_pool_member_ctx(mp_pool* p, size_t i) { return p && i < p->members.size() ? p->members[i].ctx : nullptr; }
+
+static void pool_table_release(mp_pool_table* pt) {
+  // the members that borrow fixed-base tables first, their owners last
+  for (size_t i = 0; i < pt->tables.size(); ++i)
+    if (pt->owner[i] != (int)i) mp_table_destroy(pt->tables[i]);
+  for (size_t i = 0; i < pt->tables.size(); ++i)
+    if (pt->owner[i] == (int)i) mp_table_destroy(pt->tables[i]);
+  delete pt;
+}
+int mp_pool_table_create(mp_pool* p, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* shared_key, uint32_t fb_window_bits,
+                         mp_pool_table** out) {
+  if (!p || !params || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_table_create: null pointer");
+  MP_TRY
+  std::lock_guard<std::mutex> lk(p->mu);
+  const size_t M = p->members.size();
+  mp_pool_table* pt = new mp_pool_table();
+  pt->pool = p;
+  pt->tables.assign(M, nullptr);
+  pt->owner.assign(M, 0);
+  pt->stats.resize(M);
+  for (size_t i = 0; i < M; ++i) {
+    size_t o = 0;
+    while (p->members[o].device != p->members[i].device) ++o;      // (the first member of that device: o <= i)
+    pt->owner[i] = (int)o;
+    if (o == i) pt->builds++;
+  }
+  const uint8_t* key = shared_key ? shared_key : params;      // keyless, as mp_table_create_params: G stands in for the unused key
+  std::vector<PoolResult> res;
+  int rc = MP_OK;
+  size_t bad = 0;
+  // the owners build, one per device and all at once; then -- every build has been synchronised by its own call -- the borrowers
+  for (int phase = 0; phase < 2 && rc == MP_OK; ++phase) {
+    p->run(M, [&](size_t i) {
+      const bool owns = pt->owner[i] == (int)i;
+      if (owns != (phase == 0)) return (int)MP_OK;
+      const int r = table_create(p->members[i].ctx, m, n, params, key, fb_window_bits, owns ? nullptr : pt->tables[pt->owner[i]], &pt->tables[i]);
+      if (r == MP_OK && !shared_key) pt->tables[i]->keyless = true;
+      return r;
+    }, res);
+    for (size_t i = M; i-- > 0;)
+      if (res[i].rc != MP_OK) rc = res[i].rc, bad = i;
+  }
+  if (rc != MP_OK) {
+    const std::string text = "mp_pool_table_create: " + pool_member_text(p, bad, res[bad].err);
+    pool_table_release(pt);      // (mp_table_destroy of a null table is a no-op)
+    return fail(rc, text);
+  }
+  *out = pt;
+  return MP_OK;
+  MP_CATCH
+}
+void mp_pool_table_destroy(mp_pool_table* pt) {
+  if (!pt) return;
+  std::lock_guard<std::mutex> lk(pt->pool->mu);
+  pool_table_release(pt);
+}
+mp_table* mp_pool_table_member(mp_pool_table* pt, size_t i) { return pt && i < pt->tables.size() ? pt->tables[i] : nullptr; }
+int mp_pool_set_min_shard(mp_pool_table* pt, size_t proofs) {
+  if (!pt || !proofs) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_set_min_shard: a pool table and at least 1 proof per shard");
+  std::lock_guard<std::mutex> lk(pt->pool->mu);
+  pt->min_shard = proofs;
+  return MP_OK;
+}
+int mp_pool_shuffle_and_remask_batch(mp_pool_table* pt, size_t B, const uint8_t* shared_keys, const uint8_t* decks,
+                                     const uint8_t* masking_factors, const uint32_t* permutations, const uint8_t* prover_seeds,
+                                     uint8_t* out_decks, uint8_t* out_proofs, int32_t* status) {
+  if (!pt) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_shuffle_and_remask_batch: null pool table");
+  const mp_table* t0 = pt->tables[0];
+  if (int bad = prove_batch_args(t0, B, shared_keys, decks, masking_factors, permutations, prover_seeds, out_decks, out_proofs, status)) return bad;
+  MP_TRY
+  const size_t N = t0->N, pb = t0->point_bytes, dsz = 2 * N * pb, psz = proof_size_bytes(t0->m, t0->n, t0->point_bytes);
+  return pool_dispatch(pt, B, [&](size_t i, size_t f, size_t c) {
+    mp_table* t = pt->tables[i];
+    if (shared_keys)
+      return mp_shuffle_and_remask_batch_keys(t, c, shared_keys + f * pb, decks + f * dsz, masking_factors + f * N * 32, permutations + f * N,
+                                              prover_seeds + f * 32, out_decks + f * dsz, out_proofs + f * psz, status + f);
+    return mp_shuffle_and_remask_batch(t, c, decks + f * dsz, masking_factors + f * N * 32, permutations + f * N, prover_seeds + f * 32,
+                                       out_decks + f * dsz, out_proofs + f * psz, status + f);
+  });
+  MP_CATCH
+}
+int mp_pool_verify_shuffle_batch(mp_pool_table* pt, size_t B, const uint8_t* shared_keys, const uint8_t* decks, const uint8_t* shuffled_decks,
+                                 const uint8_t* proofs, int32_t* status) {
+  if (!pt) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_verify_shuffle_batch: null pool table");
+  const mp_table* t0 = pt->tables[0];
+  if (int bad = verify_batch_args(t0, B, shared_keys, decks, shuffled_decks, proofs, status)) return bad;
+  MP_TRY
+  const size_t N = t0->N, pb = t0->point_bytes, dsz = 2 * N * pb, psz = proof_size_bytes(t0->m, t0->n, t0->point_bytes);
+  return pool_dispatch(pt, B, [&](size_t i, size_t f, size_t c) {
+    mp_table* t = pt->tables[i];
+    if (shared_keys)
+      return mp_verify_shuffle_batch_keys(t, c, shared_keys + f * pb, decks + f * dsz, shuffled_decks + f * dsz, proofs + f * psz, status + f);
+    return mp_verify_shuffle_batch(t, c, decks + f * dsz, shuffled_decks + f * dsz, proofs + f * psz, status + f);
+  });
+  MP_CATCH
+}
+int mp_pool_stats(const mp_pool_table* pt, uint64_t out[8]) {
+  if (!pt || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_stats: bad argument");
+  std::lock_guard<std::mutex> lk(pt->pool->mu);
+  const uint64_t v[8] = {pt->calls, pt->proofs, pt->last_members, pt->builds, (uint64_t)pt->tables.size(), 0, 0, 0};
+  memcpy(out, v, sizeof(v));
+  return MP_OK;
+}
+int mp_pool_member_stats(const mp_pool_table* pt, size_t i, uint64_t out[4]) {
+  if (!pt || !out || i >= pt->tables.size()) return fail(MP_ERR_BAD_ARGUMENT, "mp_pool_member_stats: bad argument");
+  std::lock_guard<std::mutex> lk(pt->pool->mu);
+  const uint64_t v[4] = {(uint64_t)pt->pool->members[i].device, pt->stats[i].calls, pt->stats[i].proofs, pt->stats[i].busy_us};
   memcpy(out, v, sizeof(v));
   return MP_OK;
 }

@@ -20,6 +20,7 @@
 #include <map>
 #include <memory>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <mutex>
 #include <vector>
@@ -40,12 +41,24 @@ template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  bool view = false;      // p belongs to another DevBuf (borrow): read-only here, never freed and never resized
   DevBuf() {}
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { rt::dfree(p); }
+  ~DevBuf() {
+    if (!view) rt::dfree(p);
+  }
+  // a non-owning view of `o`: the lanes of a pool share the fixed-base tables of their device's first member (pool.hpp), which
+  // outlives them
+  void borrow(const DevBuf& o) {
+    if (!view) rt::dfree(p);
+    p = o.p;
+    n = o.n;
+    view = true;
+  }
   void alloc(size_t count, rt::Stream s, bool zero = true) {
     if (count <= n) return;
+    if (view) throw std::logic_error("DevBuf: a borrowed buffer cannot grow");
     rt::dfree(p);
     p = nullptr;
     p = (T*)rt::dmalloc(count * sizeof(T));
@@ -220,6 +233,7 @@ struct mp_table {
   int pipeline = 0;               // > 0: device-resident verify calls run on the context's second lane, next to the prove calls, and up
                                   // to this many of their screening verdicts stay unexamined when a call returns (mp_set_pipeline)
   virtual ~mp_table() {}
+  virtual const mp::DevBuf<uint32_t>& fixed_tables() const = 0;      // the fixed-base window tables (what a pool's lanes borrow)
   virtual void flush() = 0;       // complete deferred verification passes and wait for the verify lane
   virtual void reserve(size_t B) = 0;
   virtual void set_latency_batch(size_t B) = 0;
@@ -298,7 +312,7 @@ namespace mp {
 // per-curve factories (one translation unit per curve so that the curves compile in parallel)
 #define MP_DECLARE_CURVE(NAME)                                                                                          \
   mp_table* make_table_##NAME(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* pk,           \
-                              uint32_t fb_bits, int* rc);                                                              \
+                              uint32_t fb_bits, int* rc, const mp_table* fb_from = nullptr);                           \
   int setup_##NAME(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t seed[32], uint8_t* out);                                   \
   long ser_points_##NAME(bool de, size_t count, const uint8_t* in, uint8_t* out);                                                \
   int decompress_dev_##NAME(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint8_t* d_in, uint8_t* d_out, \

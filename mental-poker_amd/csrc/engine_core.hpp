@@ -325,7 +325,8 @@ struct Table : mp_table {
   uint32_t cur_table_group = TABLE_GROUP;
   uint32_t cur_norm_chunk = NORM_CHUNK;          // points per inversion in k_normalize: a property of the plan in use
   DevBuf<uint32_t> fbpts;    // (n+5) affine base points
-  DevBuf<uint32_t> FB;       // fixed-base window tables
+  DevBuf<uint32_t> FB;       // fixed-base window tables (a view of another table's on the lanes of a pool: init)
+  const DevBuf<uint32_t>& fixed_tables() const override { return FB; }
   Workspace ws;
   bool merged_verify = true;   // verify_dev screens the batch with the merged equation first (mp_set_merged_verify)
   void set_merged_verify(bool on) override { merged_verify = on; }
@@ -450,7 +451,9 @@ struct Table : mp_table {
     psk_ready = true;
   }
 
-  int init(mp_ctx* c, uint32_t m_, uint32_t n_, const uint8_t* params, const uint8_t* pk, uint32_t fb_bits) {
+  // fb_from: a table of the same parameters, key and window width on the same device, already built and synchronised, whose fixed-base
+  // tables this one reads instead of building its own (the lanes of a pool: pool.hpp); it must outlive this table
+  int init(mp_ctx* c, uint32_t m_, uint32_t n_, const uint8_t* params, const uint8_t* pk, uint32_t fb_bits, const mp_table* fb_from = nullptr) {
     ctx = c;
     if (fb_bits != 8 && fb_bits != 16 && fb_bits != 20 && fb_bits != 21)
       return fail(MP_ERR_BAD_ARGUMENT, "fixed-base window width must be 8, 16, 20 or 21 bits");
@@ -495,7 +498,13 @@ struct Table : mp_table {
       fe_pack<F>(bases[i].y, &flat[i * G_::PW + G_::FW]);
     }
     fbpts.upload(flat, s);
-    build_fixed_tables(fb.count());
+    if (fb_from) {
+      if (fb_from->fb_bits != fb_bits || fb_from->n != n || fb_from->point_bytes != point_bytes || fb_from->ctx->device != ctx->device)
+        return fail(MP_ERR_INTERNAL, "shared fixed-base tables: geometry or device mismatch");
+      FB.borrow(fb_from->fixed_tables());
+    } else {
+      build_fixed_tables(fb.count());
+    }
 
     build_plans(ps, false);
     // Blake2s("Shuffle Proof")  [REF mod.rs:84]
@@ -3018,9 +3027,9 @@ static int decompress_device(mp_ctx* ctx, size_t groups, uint32_t per_group, uin
 #define MP_DEFINE_CURVE(NAME)                                                                                  \
   namespace mp {                                                                                               \
   mp_table* make_table_##NAME(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t* params, const uint8_t* pk,  \
-                              uint32_t fb_bits, int* rc) {                                                     \
+                              uint32_t fb_bits, int* rc, const mp_table* fb_from) {                            \
     std::unique_ptr<Table<NAME>> p(new Table<NAME>());      /* (an init that throws -- out of memory -- gives everything back) */ \
-    *rc = p->init(ctx, m, n, params, pk, fb_bits);                                                             \
+    *rc = p->init(ctx, m, n, params, pk, fb_bits, fb_from);                                                    \
     return p.release();                                                                                        \
   }                                                                                                            \
   int setup_##NAME(mp_ctx* ctx, uint32_t m, uint32_t n, const uint8_t seed[32], uint8_t* out) {                \

@@ -114,10 +114,21 @@ class DLCards:
     """`impl BarnettSmartProtocol for DLCards<C>` -- hot-path members only (setup, shuffle_and_remask,
     verify_shuffle and their batched forms).  One instance = one curve on one GPU."""
 
-    def __init__(self, curve="stark", device=0, fb_bits=8, coalesce=None, sigma_screen=None):
+    def __init__(self, curve="stark", device=0, fb_bits=8, coalesce=None, sigma_screen=None, devices=None):
         self.curve = curve
         self.fb_bits = fb_bits      # fixed-base window width of the table contexts (8: compact, 16: throughput)
-        self.engine = _native.Engine(curve, device)
+        # devices = [d0, d1, ...]: a pool of contexts (_native.Pool; a device named several times gives lanes on it).  The four batched
+        # shuffle members cut their proofs into blocks over the pool's members -- same bytes, same status words --, everything else runs
+        # on member 0 (`device` is not used then).  None: one context on `device`, as before.
+        self.pool = None
+        if devices is not None:
+            try:
+                self.pool = _native.Pool(curve, devices)
+            except _native.NoDeviceError:
+                raise
+            except _native.NativeError as e:
+                raise CardProtocolError.io(str(e))
+        self.engine = self.pool.engine(0) if self.pool is not None else _native.Engine(curve, device)
         self._tables = {}
         # coalesce = (max_batch, max_wait_us): shuffle_and_remask / verify_shuffle of every aggregate key go to ONE table of the
         # parameters per (m, n, params), through the keyed single-proof calls with coalescing on -- concurrent callers (threads) share its
@@ -174,13 +185,21 @@ class DLCards:
         t = self._tables.get(key)
         if t is None:
             try:
-                t = self.engine.table(pp.m, pp.n, pp.raw, shared_key, self.fb_bits)
+                if self.pool is not None:      # member 0's table, with the pool table it belongs to
+                    pt = self.pool.table(pp.m, pp.n, pp.raw, shared_key, self.fb_bits)
+                    t = pt.member(0)
+                    t.pool_table = pt
+                else:
+                    t = self.engine.table(pp.m, pp.n, pp.raw, shared_key, self.fb_bits)
                 if self.sigma_screen is not None:
                     t.set_sigma_screen(*self.sigma_screen)
             except _native.NativeError as e:
                 raise CardProtocolError.io(str(e))
             if len(self._tables) >= 4:
-                self._tables.pop(next(iter(self._tables))).close()
+                old = self._tables.pop(next(iter(self._tables)))
+                old.close()
+                if getattr(old, "pool_table", None) is not None:
+                    old.pool_table.close()
             self._tables[key] = t
         return t
 
@@ -486,9 +505,9 @@ class DLCards:
         t = self.table(pp, shared_key)
         perms = [v for p in permutations for v in p.mapping]
         try:
-            d, p, st = t.shuffle_and_remask_batch(b"".join(b"".join(dk) for dk in decks),
-                                                  b"".join(_scalar_bytes(f) for f in masking_factors), perms,
-                                                  b"".join(rng_seeds))
+            d, p, st = getattr(t, "pool_table", t).shuffle_and_remask_batch(b"".join(b"".join(dk) for dk in decks),
+                                                                           b"".join(_scalar_bytes(f) for f in masking_factors), perms,
+                                                                           b"".join(rng_seeds))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         N, ps, cb = pp.m * pp.n, t.proof_bytes, 2 * self.engine.point_bytes
@@ -506,8 +525,13 @@ class DLCards:
         t = self.table(pp, shared_keys[0])
         perms = [v for p in permutations for v in p.mapping]
         try:
-            d, p, st = t.shuffle_and_remask_batch_keys(b"".join(shared_keys), b"".join(b"".join(dk) for dk in decks),
-                                                       b"".join(_scalar_bytes(f) for f in masking_factors), perms, b"".join(rng_seeds))
+            if getattr(t, "pool_table", None) is not None:
+                d, p, st = t.pool_table.shuffle_and_remask_batch(b"".join(b"".join(dk) for dk in decks),
+                                                                 b"".join(_scalar_bytes(f) for f in masking_factors), perms,
+                                                                 b"".join(rng_seeds), keys=b"".join(shared_keys))
+            else:
+                d, p, st = t.shuffle_and_remask_batch_keys(b"".join(shared_keys), b"".join(b"".join(dk) for dk in decks),
+                                                           b"".join(_scalar_bytes(f) for f in masking_factors), perms, b"".join(rng_seeds))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         N, ps, cb = pp.m * pp.n, t.proof_bytes, 2 * self.engine.point_bytes
@@ -522,8 +546,13 @@ class DLCards:
     def verify_shuffle_batch_keys(self, pp, shared_keys, original_decks, shuffled_decks, proofs):
         t = self.table(pp, shared_keys[0])
         try:
-            st = t.verify_shuffle_batch_keys(b"".join(shared_keys), b"".join(b"".join(d) for d in original_decks),
-                                             b"".join(b"".join(d) for d in shuffled_decks), b"".join(proofs))
+            if getattr(t, "pool_table", None) is not None:
+                st = t.pool_table.verify_shuffle_batch(b"".join(b"".join(d) for d in original_decks),
+                                                       b"".join(b"".join(d) for d in shuffled_decks), b"".join(proofs),
+                                                       keys=b"".join(shared_keys))
+            else:
+                st = t.verify_shuffle_batch_keys(b"".join(shared_keys), b"".join(b"".join(d) for d in original_decks),
+                                                 b"".join(b"".join(d) for d in shuffled_decks), b"".join(proofs))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         return [None if s == 0 else (CryptoError(self.engine.check_name(s)) if s > 0 else CardProtocolError.io(self.engine.check_name(s)))
@@ -585,8 +614,8 @@ class DLCards:
     def verify_shuffle_batch(self, pp, shared_key, original_decks, shuffled_decks, proofs):
         t = self.table(pp, shared_key)
         try:
-            st = t.verify_shuffle_batch(b"".join(b"".join(d) for d in original_decks),
-                                        b"".join(b"".join(d) for d in shuffled_decks), b"".join(proofs))
+            st = getattr(t, "pool_table", t).verify_shuffle_batch(b"".join(b"".join(d) for d in original_decks),
+                                                                 b"".join(b"".join(d) for d in shuffled_decks), b"".join(proofs))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         res = []
