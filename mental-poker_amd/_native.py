@@ -55,7 +55,7 @@ SOURCES = ["capi.hip"] + [f % c for c in ("stark", "bn254", "secp256k1", "bls12_
 def build(verbose=False):
     """compile the HIP engine for gfx950 in-tree -> mental-poker_amd/libmpshuffle.so
     (one translation unit per curve, compiled in parallel, objects cached under csrc/_obj), and beside it the test tools
-    tools/quadcheck/quad_check, tools/primcheck/libprimcheck.so and tools/fscheck/libfscheck.so"""
+    tools/quadcheck/quad_check, tools/primcheck/libprimcheck.so, tools/fscheck/libfscheck.so and tools/digitcheck/libdigitcheck.so"""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(HERE, "csrc")
     objdir = os.path.join(csrc, "_obj")
@@ -103,9 +103,14 @@ def build(verbose=False):
     fs_src = os.path.join(fs_dir, "fs_check.hip")
     fs_lib = os.path.join(fs_dir, "libfscheck.so")
 
+    dg_dir = os.path.join(ROOT, "tools", "digitcheck")
+    dg_src = os.path.join(dg_dir, "digit_check.hip")
+    dg_lib = os.path.join(dg_dir, "libdigitcheck.so")
+
     def compile_probe(curve_id, probe_dir=probe_dir, probe_src=probe_src, stem="prim_check", macro="PRIM_CURVE"):
         """tools/primcheck/prim_check.hip: one field / group operation per lane, for tests/test_gpu_primitives.py; tools/fscheck/fs_check.hip:
-        the Fiat-Shamir layer and the screening weights, for tests/test_gpu_fs.py.  One object per curve, with EXACTLY the library's flags
+        the Fiat-Shamir layer and the screening weights, for tests/test_gpu_fs.py; tools/digitcheck/digit_check.hip: the scalar recodings, for
+        tests/test_gpu_digit.py.  One object per curve, with EXACTLY the library's flags
         (the code generation under test is the library's); shared objects of their own, nothing of them goes into libmpshuffle.so"""
         os.makedirs(os.path.join(probe_dir, "_obj"), exist_ok=True)
         obj = os.path.join(probe_dir, "_obj", "%s_%d.o" % (stem, curve_id))
@@ -119,12 +124,13 @@ def build(verbose=False):
 
     # The library's translation units are queued first and the library is linked as soon as THEY are done; the probe's objects
     # share the pool and are collected afterwards, so the library never waits for the probe's link (they do compete for cores).
-    ex = ThreadPoolExecutor(max_workers=len(SOURCES) + 1 + 2 * len(CURVE_IDS))
+    ex = ThreadPoolExecutor(max_workers=len(SOURCES) + 1 + 3 * len(CURVE_IDS))
     try:
         res_f = [ex.submit(compile_one, s) for s in SOURCES]
         chk = ex.submit(compile_check)
         probe_f = [ex.submit(compile_probe, k) for k in sorted(CURVE_IDS.values())] if os.path.exists(probe_src) else []
         fs_f = [ex.submit(compile_probe, k, fs_dir, fs_src, "fs_check", "FS_CURVE") for k in sorted(CURVE_IDS.values())] if os.path.exists(fs_src) else []
+        dg_f = [ex.submit(compile_probe, k, dg_dir, dg_src, "digit_check", "DIGIT_CURVE") for k in sorted(CURVE_IDS.values())] if os.path.exists(dg_src) else []
         res = [f.result() for f in res_f]
         objs = [r[0] for r in res]
         if any(r[1] for r in res) or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(o) for o in objs):
@@ -135,9 +141,10 @@ def build(verbose=False):
         chk.result()
         probe = [f.result() for f in probe_f]      # (a probe that does not compile fails the build: its tests do not skip)
         fs_probe = [f.result() for f in fs_f]
+        dg_probe = [f.result() for f in dg_f]
     finally:
         ex.shutdown(wait=True)
-    for objs_p, lib_p in ((probe, probe_lib), (fs_probe, fs_lib)):
+    for objs_p, lib_p in ((probe, probe_lib), (fs_probe, fs_lib), (dg_probe, dg_lib)):
         if objs_p and (any(r[1] for r in objs_p) or not os.path.exists(lib_p)
                        or os.path.getmtime(lib_p) < max(os.path.getmtime(r[0]) for r in objs_p)):
             cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_p] + [r[0] for r in objs_p]
