@@ -119,6 +119,46 @@ class DLCardsT {
     if (mp_proof_deserialize(curve_, pp.m, pp.n, bytes.data(), bytes.size(), proof.data()) != MP_OK) throw CardProtocolError(mp_last_error());
     return proof;
   }
+  // The same for batches held as canonical bytes, converted ON THE DEVICE (mpshuffle.h "canonical serialisation"): `data` = B proofs of
+  // serialized_size(pp) bytes / D decks of mp_serialized_deck_size bytes, back to back.  Status words are returned, not thrown: 0, or
+  // MP_ERR_BAD_ENCODING for an entry that is refused (its refused elements are zero bytes in `wire`)
+  struct Deserialized {
+    std::vector<uint8_t> wire;
+    std::vector<int32_t> status;
+  };
+  Deserialized deserialize_proofs(const Parameters& pp, const std::vector<uint8_t>& data) {
+    const size_t B = serialized_size(pp) ? data.size() / serialized_size(pp) : 0;
+    if (!B || B * serialized_size(pp) != data.size()) throw CardProtocolError("whole serialised proofs expected");
+    Deserialized r{std::vector<uint8_t>(B * mp_proof_size_curve(curve_, pp.m, pp.n)), std::vector<int32_t>(B)};
+    if (mp_proofs_deserialize_batch(ctx_, pp.m, pp.n, B, data.data(), r.wire.data(), r.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return r;
+  }
+  Deserialized deserialize_decks(const Parameters& pp, const std::vector<uint8_t>& data) {
+    const size_t cards = (size_t)pp.m * pp.n, sz = mp_serialized_deck_size(curve_, cards), D = data.size() / sz;
+    if (!D || D * sz != data.size()) throw CardProtocolError("whole serialised decks expected");
+    Deserialized r{std::vector<uint8_t>(D * cards * 2 * PB), std::vector<int32_t>(D)};
+    if (mp_decks_deserialize_batch(ctx_, D, cards, data.data(), r.wire.data(), r.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return r;
+  }
+  // device pointers: pass-throughs on this instance's context (mp_points_serialize_dev, mp_deck_serialize_dev, mp_proof_serialize_dev,
+  // mp_proof_deserialize_dev); enqueued, final after sync()
+  void points_serialize_dev(size_t count, const void* d_wire_points, void* d_out, void* d_status) {
+    if (mp_points_serialize_dev(ctx_, count, d_wire_points, d_out, d_status) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  void deck_serialize_dev(size_t decks, size_t cards, const void* d_wire_decks, void* d_out, void* d_status) {
+    if (mp_deck_serialize_dev(ctx_, decks, cards, d_wire_decks, d_out, d_status) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  void proof_serialize_dev(const Parameters& pp, size_t B, const void* d_proofs_wire, void* d_out, void* d_status) {
+    if (mp_proof_serialize_dev(ctx_, pp.m, pp.n, B, d_proofs_wire, d_out, d_status) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  void proof_deserialize_dev(const Parameters& pp, size_t B, const void* d_data, void* d_out_proofs_wire, void* d_status) {
+    if (mp_proof_deserialize_dev(ctx_, pp.m, pp.n, B, d_data, d_out_proofs_wire, d_status) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  void sync() {
+    if (mp_sync(ctx_) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
 
   // Opening cards in batches (mpshuffle.h "opening cards"): compute_reveal_token / unmask [REF mod.rs:300-378] for the T tokens of
   // many cards in one call each.  signer[c T + j] = index into keys of the player whose token j of card c is; tokens, proofs and

@@ -307,7 +307,8 @@ int mp_set_bucket_bits(mp_table* t, uint32_t bits);
  * status 0, out of mp_deck_validate_dev with status 0, or out of this engine's own prover.  0 (default) = test everything. */
 #define MP_VALIDATED_DECKS 1u     /* the input decks of prove and verify calls */
 #define MP_VALIDATED_SHUFFLED 2u  /* the shuffled decks of verify calls */
-#define MP_VALIDATED_PROOFS 4u    /* the points of the proofs (only if they came through mp_proof_deserialize) */
+#define MP_VALIDATED_PROOFS 4u    /* the points of the proofs (only if they came through mp_proof_deserialize, or through
+                                   * mp_proof_deserialize_dev / mp_proofs_deserialize_batch with status 0) */
 int mp_set_validated(mp_table* t, uint32_t what);
 /* `decks` wire-v1 decks of the table's size in DEVICE memory -> one int32 per deck in d_status: 0, or MP_ERR_BAD_ENCODING if a point is
  * not canonical, not on the curve or outside the prime-order subgroup.  The once-per-deck validation that mp_set_validated relies on. */
@@ -616,6 +617,32 @@ int mp_proof_deserialize(int curve_id, uint32_t m, uint32_t n, const uint8_t* da
  * mp_deck_deserialize_dev is what mp_shuffle_and_remask_batch_dev / mp_verify_shuffle_batch_dev take as d_decks. */
 int mp_points_deserialize_dev(mp_ctx* ctx, size_t count, const void* d_data, void* d_out_wire_points, void* d_status);
 int mp_deck_deserialize_dev(mp_ctx* ctx, size_t decks, size_t cards, const void* d_data, void* d_out_wire_decks, void* d_status);
+/* The other three conversions of a prove-or-verify round trip on the device, in batches.  Same rules: DEVICE pointers, the context's
+ * lock, enqueued on the context's stream, final after mp_sync or any later call on the context; d_status is zeroed by the call and
+ * receives 0 or MP_ERR_BAD_ENCODING, one int32 per unit; a null pointer or a zero count is MP_ERR_BAD_ARGUMENT and enqueues nothing.
+ *   mp_points_serialize_dev   `count` wire points -> mp_serialized_point_size bytes each, the bytes of mp_points_serialize: all-zero wire
+ *                             bytes are the point at infinity, the sign bit is 2y > p; only the range of x and y is checked (as on the
+ *                             host), a coordinate >= p leaves an all-zero slot and -1 in the point's status word.
+ *   mp_deck_serialize_dev     `decks` wire decks of `cards` cards (<= 4096) -> Vec<MaskedCard> of mp_serialized_deck_size bytes each, back
+ *                             to back, u64 length in front: what mp_deck_deserialize_dev reads.  Status per deck.  The input may be the
+ *                             prover's d_out_decks.
+ *   mp_proof_serialize_dev    `B` wire proofs of mp_proof_size_curve bytes -> mp_serialized_proof_size bytes each, the bytes of
+ *                             mp_proof_serialize.  Status per proof; scalars are copied as they are (the host does not judge them here).
+ *   mp_proof_deserialize_dev  the inverse, with the validation of mp_proof_deserialize: every Vec length, every point as
+ *                             mp_points_deserialize_dev validates one, every scalar < q.  A proof reads 0 iff mp_proof_deserialize accepts
+ *                             its bytes, and then the wire bytes are the same.  Every element is converted on its own: in a proof that
+ *                             reads -1 the refused points and scalars are zero bytes and the valid elements are converted (the host form
+ *                             stops at the first error).  The output is what mp_verify_shuffle_batch_dev takes as d_proofs. */
+int mp_points_serialize_dev(mp_ctx* ctx, size_t count, const void* d_wire_points, void* d_out, void* d_status);
+int mp_deck_serialize_dev(mp_ctx* ctx, size_t decks, size_t cards, const void* d_wire_decks, void* d_out, void* d_status);
+int mp_proof_serialize_dev(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const void* d_proofs_wire, void* d_out, void* d_status);
+int mp_proof_deserialize_dev(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const void* d_data, void* d_out_proofs_wire, void* d_status);
+/* HOST buffers, conversion on the device: one upload, mp_deck_deserialize_dev / mp_proof_deserialize_dev, one download; bytes and
+ * statuses are theirs, and the call returns with both in place.  For a caller without device buffers: bulk data never meets the host's
+ * square root.  Buffers from mp_host_alloc are copied asynchronously, pageable ones work too.  These calls are never coalesced; their
+ * device staging stays with the context. */
+int mp_decks_deserialize_batch(mp_ctx* ctx, size_t decks, size_t cards, const uint8_t* data, uint8_t* out_wire_decks, int32_t* status);
+int mp_proofs_deserialize_batch(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const uint8_t* data, uint8_t* out_proofs_wire, int32_t* status);
 
 /* ---- measurement hooks ---------------------------------------------------------------------------------------
  * With profiling on, every kernel launch is bracketed by HIP events on the context's stream;

@@ -36,6 +36,8 @@ SYMBOLS = [
     "mp_serialized_point_size", "mp_serialized_deck_size", "mp_serialized_params_size", "mp_serialized_proof_size",
     "mp_points_serialize", "mp_points_deserialize", "mp_deck_serialize", "mp_deck_deserialize", "mp_params_serialize",
     "mp_params_deserialize", "mp_proof_serialize", "mp_proof_deserialize", "mp_points_deserialize_dev", "mp_deck_deserialize_dev",
+    "mp_points_serialize_dev", "mp_deck_serialize_dev", "mp_proof_serialize_dev", "mp_proof_deserialize_dev",
+    "mp_decks_deserialize_batch", "mp_proofs_deserialize_batch",
 ]
 
 
@@ -305,6 +307,12 @@ def bind(cdll):
     cdll.mp_deck_deserialize_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
     cdll.mp_proof_serialize.argtypes = [c.c_int, c.c_uint32, c.c_uint32, u8p, u8p]
     cdll.mp_proof_deserialize.argtypes = [c.c_int, c.c_uint32, c.c_uint32, u8p, c.c_size_t, u8p]
+    cdll.mp_points_serialize_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    cdll.mp_deck_serialize_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    cdll.mp_proof_serialize_dev.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    cdll.mp_proof_deserialize_dev.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    cdll.mp_decks_deserialize_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, u8p, u8p, i32p]
+    cdll.mp_proofs_deserialize_batch.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.c_size_t, u8p, u8p, i32p]
     return cdll
 
 
@@ -469,6 +477,59 @@ class Engine:
     def deck_deserialize_dev(self, decks, cards, d_data, d_out_wire_decks, d_status):
         """`decks` serialised Vec<MaskedCard> of `cards` cards each (device memory) -> wire decks; d_status: one int32 per deck"""
         self._chk(self.lib.mp_deck_deserialize_dev(self.h, decks, cards, d_data, d_out_wire_decks, d_status))
+
+    def points_serialize_dev(self, count, d_wire, d_out, d_status):
+        """wire v1 points in device memory -> compressed arkworks points in device memory; d_status: one int32 per point"""
+        self._chk(self.lib.mp_points_serialize_dev(self.h, count, d_wire, d_out, d_status))
+
+    def deck_serialize_dev(self, decks, cards, d_wire_decks, d_out, d_status):
+        """`decks` wire decks of `cards` cards each (device memory) -> serialised Vec<MaskedCard>; d_status: one int32 per deck"""
+        self._chk(self.lib.mp_deck_serialize_dev(self.h, decks, cards, d_wire_decks, d_out, d_status))
+
+    def proof_serialize_dev(self, m, n, B, d_proofs_wire, d_out, d_status):
+        """`B` wire proofs of shape (m, n) (device memory) -> canonical proofs; d_status: one int32 per proof"""
+        self._chk(self.lib.mp_proof_serialize_dev(self.h, m, n, B, d_proofs_wire, d_out, d_status))
+
+    def proof_deserialize_dev(self, m, n, B, d_data, d_out_proofs_wire, d_status):
+        """`B` canonical proofs of shape (m, n) (device memory) -> wire proofs, validated; d_status: one int32 per proof"""
+        self._chk(self.lib.mp_proof_deserialize_dev(self.h, m, n, B, d_data, d_out_proofs_wire, d_status))
+
+    def _deserialize_batch(self, call, units, in_size, out_size, data, pinned):
+        """host bytes -> (wire bytes, [status per unit]) through a *_deserialize_batch entry point; pinned: stage the call's buffers in
+        page-locked memory from mp_host_alloc"""
+        if units < 1 or len(data) != units * in_size:
+            raise NativeError(MP_ERR_BAD_ARGUMENT, "deserialize batch: %d bytes for %d units of %d" % (len(data), units, in_size))
+        st = (ctypes.c_int32 * units)()
+        if not pinned:
+            out = (ctypes.c_uint8 * (units * out_size))()
+            self._chk(call(_in(data), out, st))
+            return bytes(out), list(st)
+        sizes = (units * in_size, units * out_size, 4 * units)
+        bufs = [self.lib.mp_host_alloc(k) for k in sizes]
+        try:
+            if not all(bufs):
+                raise NativeError(MP_ERR_INTERNAL, "mp_host_alloc failed")
+            ctypes.memmove(bufs[0], bytes(data), sizes[0])
+            self._chk(call(bufs[0], bufs[1], bufs[2]))
+            return ctypes.string_at(bufs[1], sizes[1]), list((ctypes.c_int32 * units).from_buffer_copy(ctypes.string_at(bufs[2], sizes[2])))
+        finally:
+            for b in bufs:
+                if b:
+                    self.lib.mp_host_free(ctypes.c_void_p(b))
+
+    def decks_deserialize_batch(self, decks, cards, data, pinned=False):
+        """`decks` serialised Vec<MaskedCard> of `cards` cards, back to back in host bytes -> (wire decks, [status per deck]); the
+        conversion runs on the device (mp_decks_deserialize_batch)"""
+        cid = CURVE_IDS[self.curve]
+        return self._deserialize_batch(lambda i, o, s: self.lib.mp_decks_deserialize_batch(self.h, decks, cards, i, o, s), decks,
+                                       self.lib.mp_serialized_deck_size(cid, cards), 2 * cards * self.point_bytes, data, pinned)
+
+    def proofs_deserialize_batch(self, m, n, B, data, pinned=False):
+        """`B` canonical proofs of shape (m, n), back to back in host bytes -> (wire proofs, [status per proof]); the conversion runs
+        on the device (mp_proofs_deserialize_batch)"""
+        cid = CURVE_IDS[self.curve]
+        return self._deserialize_batch(lambda i, o, s: self.lib.mp_proofs_deserialize_batch(self.h, m, n, B, i, o, s), B,
+                                       self.lib.mp_serialized_proof_size(cid, m, n), self.lib.mp_proof_size_curve(cid, m, n), data, pinned)
 
     def profile_enable(self, on=True):
         self._chk(self.lib.mp_profile_enable(self.h, 1 if on else 0))

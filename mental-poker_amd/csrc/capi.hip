@@ -3,6 +3,7 @@
 // [REF barnett-smart-card-protocol/src/discrete_log_cards/mod.rs:105-121, 380-418, 420-443].
 #include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "engine_base.hpp"
 #include "coalesce.hpp"
@@ -1554,6 +1555,119 @@ int mp_proof_deserialize(int curve_id, uint32_t m, uint32_t n, const uint8_t* da
     }
   }
   return MP_OK;
+}
+
+// ---- the remaining conversions on the device (kernels_canonical.hpp): wire -> canonical for points, decks and proofs, canonical ->
+// wire for proofs; then the two host-buffer forms that upload, convert and download
+static int compress_dev(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const void* d_in, void* d_out, void* d_status) {
+  MP_TRY
+  MP_ENTER(ctx);
+  switch (ctx->curve) {
+    case 0: return compress_dev_Stark(ctx, groups, per_group, prefix, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    case 1: return compress_dev_Bn254(ctx, groups, per_group, prefix, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    case 3: return compress_dev_Bls12_377(ctx, groups, per_group, prefix, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    default: return compress_dev_Secp256k1(ctx, groups, per_group, prefix, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+  }
+  MP_CATCH
+}
+// the element table of proof_schema(m, n) on the context (kernels_canonical.hpp: {canonical offset, wire offset, Vec length or 0}
+// per element, points first): rebuilt when the shape changes, uploaded on the context's stream behind the kernels that read the old one
+static void canon_table(mp_ctx* ctx, uint32_t m, uint32_t n, uint32_t* np, uint32_t* ns) {
+  *np = 11 * m + 8;
+  *ns = 5 * n + 9;
+  if (ctx->cn_m == m && ctx->cn_n == n) return;
+  const uint32_t pb = (uint32_t)mp_point_size(ctx->curve), cb = (uint32_t)mp_serialized_point_size(ctx->curve);
+  std::vector<uint32_t> pts, scs;
+  uint32_t co = 0, wo = 0;
+  for (const Group& g : proof_schema(m, n)) {
+    if (g.vec) co += 8;
+    std::vector<uint32_t>& t = g.point ? pts : scs;
+    const uint32_t cs = g.point ? cb : 32u, ws = g.point ? pb : 32u;
+    for (uint32_t i = 0; i < g.count; ++i) {
+      t.push_back(co);
+      t.push_back(wo);
+      t.push_back(g.vec && i == 0 ? g.vec_len : 0u);
+      co += cs;
+      wo += ws;
+    }
+  }
+  if (pts.size() != 3 * (size_t)*np || scs.size() != 3 * (size_t)*ns) throw std::logic_error("proof schema: element count");
+  ctx->cn_m = ctx->cn_n = 0;
+  ctx->cn_tab_host = pts;
+  ctx->cn_tab_host.insert(ctx->cn_tab_host.end(), scs.begin(), scs.end());
+  ctx->cn_tab.upload(ctx->cn_tab_host, ctx->stream);
+  rt::stream_sync(ctx->stream);      // (the host copy may be replaced by the next shape)
+  ctx->cn_m = m;
+  ctx->cn_n = n;
+}
+static int proof_convert_dev(mp_ctx* ctx, bool de, uint32_t m, uint32_t n, size_t B, const void* d_in, void* d_out, void* d_status) {
+  MP_TRY
+  MP_ENTER(ctx);
+  uint32_t np, ns;
+  canon_table(ctx, m, n, &np, &ns);
+  const uint32_t cs = (uint32_t)mp_serialized_proof_size(ctx->curve, m, n), ws = (uint32_t)mp_proof_size_curve(ctx->curve, m, n);
+  switch (ctx->curve) {
+    case 0: return proof_convert_dev_Stark(ctx, de, np, ns, cs, ws, B, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    case 1: return proof_convert_dev_Bn254(ctx, de, np, ns, cs, ws, B, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    case 3: return proof_convert_dev_Bls12_377(ctx, de, np, ns, cs, ws, B, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+    default: return proof_convert_dev_Secp256k1(ctx, de, np, ns, cs, ws, B, (const uint8_t*)d_in, (uint8_t*)d_out, (int32_t*)d_status);
+  }
+  MP_CATCH
+}
+// shapes whose proofs the 32-bit offsets of the element table address
+static bool proof_shape_ok(uint32_t m, uint32_t n) { return m >= 2 && n >= 2 && m <= (1u << 20) && n <= (1u << 20); }
+
+int mp_points_serialize_dev(mp_ctx* ctx, size_t count, const void* d_wire_points, void* d_out, void* d_status) {
+  if (!ctx || !count || !d_wire_points || !d_out || !d_status) return fail(MP_ERR_BAD_ARGUMENT, "mp_points_serialize_dev: bad argument");
+  return compress_dev(ctx, count, 1, 0, d_wire_points, d_out, d_status);
+}
+int mp_deck_serialize_dev(mp_ctx* ctx, size_t decks, size_t cards, const void* d_wire_decks, void* d_out, void* d_status) {
+  if (!ctx || !decks || !cards || cards > 4096 || !d_wire_decks || !d_out || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_deck_serialize_dev: bad argument");
+  return compress_dev(ctx, decks, (uint32_t)(2 * cards), 8, d_wire_decks, d_out, d_status);
+}
+int mp_proof_serialize_dev(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const void* d_proofs_wire, void* d_out, void* d_status) {
+  if (!ctx || !B || !d_proofs_wire || !d_out || !d_status || !proof_shape_ok(m, n))
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_proof_serialize_dev: bad argument");
+  return proof_convert_dev(ctx, false, m, n, B, d_proofs_wire, d_out, d_status);
+}
+int mp_proof_deserialize_dev(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const void* d_data, void* d_out_proofs_wire, void* d_status) {
+  if (!ctx || !B || !d_data || !d_out_proofs_wire || !d_status || !proof_shape_ok(m, n))
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_proof_deserialize_dev: bad argument");
+  return proof_convert_dev(ctx, true, m, n, B, d_data, d_out_proofs_wire, d_status);
+}
+// host buffers: one upload, the _dev conversion, one download -- all on the context's stream, finished when the call returns.  The
+// staging buffers stay with the context and grow to the largest call
+static int deserialize_batch(mp_ctx* ctx, size_t units, size_t in_bytes, size_t out_bytes, const uint8_t* data, uint8_t* out, int32_t* status,
+                             const std::function<int(void*, void*, void*)>& convert) {
+  MP_TRY
+  MP_ENTER(ctx);
+  ctx->cn_in.alloc(in_bytes, ctx->stream, false);
+  ctx->cn_out.alloc(out_bytes, ctx->stream, false);
+  ctx->cn_status.alloc(units, ctx->stream, false);
+  rt::h2d(ctx->cn_in.p, data, in_bytes, ctx->stream);
+  const int rc = convert(ctx->cn_in.p, ctx->cn_out.p, ctx->cn_status.p);
+  if (rc == MP_OK) {
+    rt::d2h(out, ctx->cn_out.p, out_bytes, ctx->stream);
+    rt::d2h(status, ctx->cn_status.p, units * sizeof(int32_t), ctx->stream);
+  }
+  rt::stream_sync(ctx->stream);
+  return rc;
+  MP_CATCH
+}
+int mp_decks_deserialize_batch(mp_ctx* ctx, size_t decks, size_t cards, const uint8_t* data, uint8_t* out_wire_decks, int32_t* status) {
+  if (!ctx || !decks || !cards || cards > 4096 || !data || !out_wire_decks || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_decks_deserialize_batch: bad argument");
+  return deserialize_batch(ctx, decks, decks * mp_serialized_deck_size(ctx->curve, cards), decks * 2 * cards * mp_point_size(ctx->curve), data,
+                           out_wire_decks, status,
+                           [&](void* d_in, void* d_out, void* d_st) { return mp_deck_deserialize_dev(ctx, decks, cards, d_in, d_out, d_st); });
+}
+int mp_proofs_deserialize_batch(mp_ctx* ctx, uint32_t m, uint32_t n, size_t B, const uint8_t* data, uint8_t* out_proofs_wire, int32_t* status) {
+  if (!ctx || !B || !data || !out_proofs_wire || !status || !proof_shape_ok(m, n))
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_proofs_deserialize_batch: bad argument");
+  return deserialize_batch(ctx, B, B * mp_serialized_proof_size(ctx->curve, m, n), B * mp_proof_size_curve(ctx->curve, m, n), data,
+                           out_proofs_wire, status,
+                           [&](void* d_in, void* d_out, void* d_st) { return mp_proof_deserialize_dev(ctx, m, n, B, d_in, d_out, d_st); });
 }
 
 }

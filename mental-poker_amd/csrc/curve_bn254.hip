@@ -4,5 +4,6 @@ namespace mp {
 MP_MSM_KERNELS(extern template, Bn254)
 MP_BUCKET_KERNELS(extern template, Bn254)
 MP_DECOMPRESS_KERNELS(extern template, Bn254)
+MP_CANONICAL_KERNELS(extern template, Bn254)
 }
 MP_DEFINE_CURVE(Bn254)

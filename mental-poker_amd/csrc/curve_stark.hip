@@ -4,5 +4,6 @@ namespace mp {
 MP_MSM_KERNELS(extern template, Stark)
 MP_BUCKET_KERNELS(extern template, Stark)
 MP_DECOMPRESS_KERNELS(extern template, Stark)
+MP_CANONICAL_KERNELS(extern template, Stark)
 }
 MP_DEFINE_CURVE(Stark)

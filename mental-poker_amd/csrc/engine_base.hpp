@@ -151,6 +151,13 @@ struct mp_ctx {
   mp::DevBuf<uint32_t> sq_ghalf, sq_hh, sq_rr, sq_chain;
   uint32_t sq_geom[4] = {0, 0, 0, 0};     // S, w, k, bits of the fixed exponent; S = 0: not built yet
   uint32_t sq_exp[12] = {0};
+  // the other canonical conversions (kernels_canonical.hpp): the element table of the last proof shape converted -- np point and ns
+  // scalar entries, kept on the host too (the upload reads it) -- and the device staging of the host-buffer forms (mp_*_deserialize_batch)
+  mp::DevBuf<uint32_t> cn_tab;
+  std::vector<uint32_t> cn_tab_host;
+  uint32_t cn_m = 0, cn_n = 0;
+  mp::DevBuf<uint8_t> cn_in, cn_out;
+  mp::DevBuf<int32_t> cn_status;
   mp::Profiler prof;
   // persistent waves of the bucket kernel (kernels_bucket.hpp): 8 per CU -- two workgroups of four, what its registers allow
   uint32_t bk_slots = 0;              // (engine_core.hpp bucket_slots(): BK_WAVES_PER_CU x CUs, queried once)
@@ -317,6 +324,10 @@ namespace mp {
   long ser_points_##NAME(bool de, size_t count, const uint8_t* in, uint8_t* out);                                                \
   int decompress_dev_##NAME(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint8_t* d_in, uint8_t* d_out, \
                             int32_t* d_status);                                                                                   \
+  int compress_dev_##NAME(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint8_t* d_in, uint8_t* d_out,   \
+                          int32_t* d_status);                                                                                     \
+  int proof_convert_dev_##NAME(mp_ctx* ctx, bool de, uint32_t np, uint32_t ns, uint32_t canon_stride, uint32_t wire_stride,       \
+                               size_t B, const uint8_t* d_in, uint8_t* d_out, int32_t* d_status);                                 \
   bool ser_scalars_ok_##NAME(size_t count, const uint8_t* in);
 MP_DECLARE_CURVE(Stark)
 MP_DECLARE_CURVE(Bn254)

@@ -3,7 +3,7 @@
 #pragma once
 #include "engine_base.hpp"
 #include "kernels_bucket.hpp"
-#include "kernels_decompress.hpp"
+#include "kernels_canonical.hpp"
 #include "kernels_sigma.hpp"
 #include "kernels_open.hpp"
 #include "kernels_deal.hpp"
@@ -3022,6 +3022,68 @@ static int decompress_device(mp_ctx* ctx, size_t groups, uint32_t per_group, uin
   return MP_OK;
 }
 
+// ---- the other canonical conversions on the device (kernels_canonical.hpp).  Launches of up to 2^22 elements: nothing here has a scratch
+// column, the cut only keeps the grid of a launch small
+static const size_t CANON_LAUNCH = (size_t)1 << 22;
+// wire -> canonical: `groups` x `per_group` points; tab = null: uniform groups behind `prefix` bytes (points: 1, 0; decks: 2 cards, 8),
+// else the proof's element table
+template <class C>
+static int compress_device(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint32_t* tab, uint32_t wire_stride,
+                           uint32_t canon_stride, const uint8_t* d_in, uint8_t* d_out, int32_t* d_status, bool zero_status) {
+  if ((uint64_t)groups * per_group >= ((uint64_t)1 << 32)) return fail(MP_ERR_BAD_ARGUMENT, "point compression: too many points for one call");
+  if (zero_status) rt::dzero(d_status, groups * sizeof(int32_t), ctx->stream);
+  CompressArgs a{};
+  a.in = d_in; a.out = d_out; a.status = d_status; a.tab = tab;
+  a.per_group = per_group; a.prefix = prefix;
+  a.wire_stride = wire_stride; a.canon_stride = canon_stride;
+  const size_t total = groups * per_group;
+  for (size_t off = 0; off < total; off += CANON_LAUNCH) {
+    a.first = (uint32_t)off;
+    MP_RUN(k_compress, C, (uint32_t)std::min(CANON_LAUNCH, total - off), 1, a);
+  }
+  return MP_OK;
+}
+// B proofs, either direction, through the context's element table (capi.hip: canon_table; np point and ns scalar entries)
+template <class C>
+static int proof_convert_device(mp_ctx* ctx, bool de, uint32_t np, uint32_t ns, uint32_t canon_stride, uint32_t wire_stride, size_t B,
+                                const uint8_t* d_in, uint8_t* d_out, int32_t* d_status) {
+  if ((uint64_t)B * np >= ((uint64_t)1 << 32) || (uint64_t)B * ns >= ((uint64_t)1 << 32))
+    return fail(MP_ERR_BAD_ARGUMENT, "proof conversion: too many proofs for one call");
+  if (de && !ctx->sq_geom[0]) build_sqrt_tables<C>(ctx);
+  rt::dzero(d_status, B * sizeof(int32_t), ctx->stream);
+  const uint32_t* tab = ctx->cn_tab.p;
+  if (!de) {
+    const int rc = compress_device<C>(ctx, B, np, 0, tab, wire_stride, canon_stride, d_in, d_out, d_status, false);
+    if (rc) return rc;
+  } else {
+    DecompressMapArgs a{};
+    a.d.in = d_in; a.d.out = d_out; a.d.status = d_status;
+    a.d.ghalf = ctx->sq_ghalf.p; a.d.hh = ctx->sq_hh.p; a.d.rr = ctx->sq_rr.p;
+    a.d.per_group = np; a.d.prefix = 0;
+    a.d.g = SqrtGeom{ctx->sq_geom[0], ctx->sq_geom[1], ctx->sq_geom[2], ctx->sq_geom[3]};
+    for (int i = 0; i < 12; ++i) a.d.e[i] = ctx->sq_exp[i];
+    a.tab = tab; a.canon_stride = canon_stride; a.wire_stride = wire_stride;
+    // the launches of decompress_device: 2^20 points each, one scratch column per lane of a launch
+    const size_t total = B * np, chunk = std::min<size_t>(total, (size_t)1 << 20);
+    if (a.d.g.k > 1) ctx->sq_chain.alloc((size_t)(a.d.g.k - 1) * chunk * C::FqP::NW, ctx->stream, false);
+    a.d.chain = ctx->sq_chain.p;
+    for (size_t off = 0; off < total; off += chunk) {
+      a.d.first = (uint32_t)off;
+      a.d.lanes = (uint32_t)std::min(chunk, total - off);
+      MP_RUN(k_decompress_map, C, a.d.lanes, 1, a);
+    }
+  }
+  ScalarMapArgs s{};
+  s.in = d_in; s.out = d_out; s.status = d_status; s.tab = tab + 3 * (size_t)np;
+  s.per_group = ns; s.canon_stride = canon_stride; s.wire_stride = wire_stride; s.de = de ? 1u : 0u;
+  const size_t total = B * ns;
+  for (size_t off = 0; off < total; off += CANON_LAUNCH) {
+    s.first = (uint32_t)off;
+    MP_RUN(k_scalar_map, C, (uint32_t)std::min(CANON_LAUNCH, total - off), 1, s);
+  }
+  return MP_OK;
+}
+
 }  // namespace mp
 
 #define MP_DEFINE_CURVE(NAME)                                                                                  \
@@ -3042,5 +3104,15 @@ static int decompress_device(mp_ctx* ctx, size_t groups, uint32_t per_group, uin
   int decompress_dev_##NAME(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint8_t* d_in,  \
                             uint8_t* d_out, int32_t* d_status) {                                               \
     return decompress_device<NAME>(ctx, groups, per_group, prefix, d_in, d_out, d_status);                     \
+  }                                                                                                            \
+  int compress_dev_##NAME(mp_ctx* ctx, size_t groups, uint32_t per_group, uint32_t prefix, const uint8_t* d_in,    \
+                          uint8_t* d_out, int32_t* d_status) {                                                 \
+    return compress_device<NAME>(ctx, groups, per_group, prefix, nullptr, per_group * Geo<NAME>::PB,           \
+                                 prefix + per_group * Ser<NAME>::CB, d_in, d_out, d_status, true);             \
+  }                                                                                                            \
+  int proof_convert_dev_##NAME(mp_ctx* ctx, bool de, uint32_t np, uint32_t ns, uint32_t canon_stride,          \
+                               uint32_t wire_stride, size_t B, const uint8_t* d_in, uint8_t* d_out,            \
+                               int32_t* d_status) {                                                            \
+    return proof_convert_device<NAME>(ctx, de, np, ns, canon_stride, wire_stride, B, d_in, d_out, d_status);   \
   }                                                                                                            \
   }

@@ -180,6 +180,34 @@ class DLCards:
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
 
+    # -- the same for batches, converted on the device (C ABI: mp_proofs_deserialize_batch / mp_decks_deserialize_batch): one entry per
+    # byte string, the wire value or a CardProtocolError.io for an entry that is refused
+    def _deserialize_many(self, entries, size, convert, wrap):
+        entries = [bytes(e) for e in entries]
+        if not entries:
+            return []
+        fits = [len(e) == size for e in entries]
+        try:
+            out, st = convert(len(entries), b"".join(e if ok else bytes(size) for e, ok in zip(entries, fits)))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        w = len(out) // len(entries)
+        return [wrap(out[k * w:(k + 1) * w]) if ok and s == 0 else
+                CardProtocolError.io(self.engine.check_name(s) if ok else "expected %d bytes, got %d" % (size, len(entries[k])))
+                for k, (ok, s) in enumerate(zip(fits, st))]
+
+    def deserialize_proofs(self, pp, proofs):
+        """canonical ZKProofShuffle byte strings of shape (pp.m, pp.n) -> wire proofs"""
+        return self._deserialize_many(proofs, self.proof_serialized_size(pp),
+                                      lambda B, data: self.engine.proofs_deserialize_batch(pp.m, pp.n, B, data), lambda b: b)
+
+    def deserialize_decks(self, pp, decks):
+        """canonical Vec<MaskedCard> byte strings of pp.m * pp.n cards -> decks (lists of wire cards)"""
+        cards, cb = pp.m * pp.n, 2 * self.engine.point_bytes
+        return self._deserialize_many(decks, self._ser().lib.mp_serialized_deck_size(_native.CURVE_IDS[self.curve], cards),
+                                      lambda D, data: self.engine.decks_deserialize_batch(D, cards, data),
+                                      lambda b: [b[i * cb:(i + 1) * cb] for i in range(cards)])
+
     def table(self, pp, shared_key):
         key = (pp.m, pp.n, pp.raw, bytes(shared_key))
         t = self._tables.get(key)
