@@ -209,7 +209,7 @@ struct Api {
 
   static int on_curve(const uint8_t* pt) {
     Pt p;
-    if (!S::pt_from_wire(pt, p)) return -1;
+    if (!S::coords_from_wire(pt, p)) return -1;
     return p.on_curve() ? 1 : 0;
   }
 

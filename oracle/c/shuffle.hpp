@@ -71,7 +71,8 @@ struct Shuffle {
       P.y.to_bytes(out + FQB);
     }
   }
-  static bool pt_from_wire(const uint8_t* in, Pt& P) {
+  // the coordinates of a wire point: false if one of them is not reduced
+  static bool coords_from_wire(const uint8_t* in, Pt& P) {
     bool allzero = true;
     for (size_t i = 0; i < PW; ++i) allzero &= in[i] == 0;
     if (allzero) {
@@ -81,6 +82,9 @@ struct Shuffle {
     P.inf = false;
     return Fq::from_bytes(in, P.x) && Fq::from_bytes(in + FQB, P.y);
   }
+  // a wire point as every call takes it: canonical coordinates of a point ON THE CURVE (include/mpshuffle.h: anything else is
+  // MP_ERR_BAD_ENCODING); membership in the prime-order subgroup is not tested here
+  static bool pt_from_wire(const uint8_t* in, Pt& P) { return coords_from_wire(in, P) && P.on_curve(); }
 
   // ---------------------------------------------------------------- group helpers
   static Pt msm(const FrVec& s, const PtVec& p) { return msm_pippenger<Cv>(s.data(), p.data(), s.size()).to_affine(); }

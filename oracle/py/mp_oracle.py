@@ -345,6 +345,7 @@ def pt_wire(P):
 
 
 def pt_from_wire(b):
+    """no validation (range, curve equation): unlike the C++ restatement's pt_from_wire, which refuses both -- oracle/README.md"""
     assert len(b) == 2 * _FQB
     if b == bytes(2 * _FQB):
         return None

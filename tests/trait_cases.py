@@ -242,9 +242,9 @@ def run_sigma_rejections(eng, coracle, curve):
             rows.append(row)
             names.append(name)
             verdict = coracle.sigma_verify(curve, nb, *row)
-            # The C++ oracle does not validate points (pt_from_wire in oracle/c/shuffle.hpp only range-checks the coordinates) and calls a
-            # point off the curve a failed equation; the engine documents MP_ERR_BAD_ENCODING for it, which is also what the shuffle
-            # verifier's tests expect of a deck point off the curve.
+            # A point off the curve: the engine documents MP_ERR_BAD_ENCODING for it, which is also what the shuffle verifier's tests
+            # expect of a deck point off the curve (the C++ oracle refuses it as well since pt_from_wire in oracle/c/shuffle.hpp tests
+            # the curve equation; before, it called such a point a failed equation).
             want.append(BAD_ENCODING if off else verdict)
             if (verdict == 0) != (name == "honest"):
                 fails.append("%s nbases %d: the oracle says %d for the case '%s'" % (curve, nb, verdict, name))
