@@ -88,6 +88,12 @@ void mp_host_free(void* p);
  * more; the first chunks of a call are smaller -- the first upload and the last download are the copies nothing overlaps -- and the chunks
  * of a verify call grow by half from one to the next, because the copy of chunk k + 1 takes about as long as the kernels of chunk k) */
 int mp_set_io_chunk(mp_table* t, size_t proofs);
+/* The chunks a host-buffer call of B proofs takes on this table under its current mp_set_io_chunk, in order: those of a prove call
+ * (mp_shuffle_and_remask_batch, its _keys and _seeded forms; verify = 0) or of a verify call (mp_verify_shuffle_batch[_keys]; verify != 0).
+ * Returns their number and writes the first `cap` sizes to out_chunks (which may be NULL when cap is 0); the sizes sum to B, none is 0 and
+ * none exceeds min(B, chunk).  Read-only: it starts no device work, and it is computed by the code the calls themselves cut their batch
+ * with.  0 for a NULL table or B = 0. */
+size_t mp_io_schedule(const mp_table* t, size_t B, int verify, size_t* out_chunks, size_t cap);
 
 /* ---- DLCards::setup [REF barnett-smart-card-protocol/src/discrete_log_cards/mod.rs:105-121] ---------------------------
  * "setup v2": G, ck_0..ck_{n-1}, H, gen -- n + 3 INDEPENDENT curve points sampled the way ark-ec's `C::rand` does from

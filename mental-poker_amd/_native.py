@@ -17,7 +17,7 @@ MP_ERR_BAD_ENCODING, MP_ERR_BAD_PERMUTATION, MP_ERR_BAD_ARGUMENT, MP_ERR_NO_DEVI
 
 SYMBOLS = [
     "mp_ctx_create", "mp_ctx_destroy", "mp_last_error", "mp_check_name", "mp_proof_size", "mp_params_size",
-    "mp_point_size", "mp_proof_size_curve", "mp_params_size_curve", "mp_set_merged_verify", "mp_set_subgroup_check", "mp_set_bucket_min", "mp_set_bucket_bits", "mp_set_bucket_split", "mp_set_validated", "mp_deck_validate_dev", "mp_set_chain_max_links", "mp_set_chain_group", "mp_set_chain_slice", "mp_chain_group_size", "mp_chain_last_slice", "mp_set_transcript_lanes", "mp_set_group_lanes", "mp_set_work_split", "mp_set_group_verify", "mp_group_size", "mp_set_group_refine", "mp_reverified_count", "mp_set_group_adapt", "mp_set_pipeline", "mp_set_plan_params", "mp_set_plan_thresholds", "mp_set_toom_cook", "mp_host_alloc", "mp_host_free", "mp_set_io_chunk", "mp_shuffle_and_remask_batch_keys", "mp_table_create_params",
+    "mp_point_size", "mp_proof_size_curve", "mp_params_size_curve", "mp_set_merged_verify", "mp_set_subgroup_check", "mp_set_bucket_min", "mp_set_bucket_bits", "mp_set_bucket_split", "mp_set_validated", "mp_deck_validate_dev", "mp_set_chain_max_links", "mp_set_chain_group", "mp_set_chain_slice", "mp_chain_group_size", "mp_chain_last_slice", "mp_set_transcript_lanes", "mp_set_group_lanes", "mp_set_work_split", "mp_set_group_verify", "mp_group_size", "mp_set_group_refine", "mp_reverified_count", "mp_set_group_adapt", "mp_set_pipeline", "mp_set_plan_params", "mp_set_plan_thresholds", "mp_set_toom_cook", "mp_host_alloc", "mp_host_free", "mp_set_io_chunk", "mp_io_schedule","mp_shuffle_and_remask_batch_keys", "mp_table_create_params",
     "mp_verify_shuffle_batch_keys", "mp_shuffle_and_remask_batch_keys_dev", "mp_verify_shuffle_batch_keys_dev",
     "mp_keyset_create", "mp_keyset_destroy", "mp_keyset_size", "mp_shuffle_and_remask_batch_keyset_dev", "mp_verify_shuffle_batch_keyset_dev",
     "mp_setup", "mp_table_create", "mp_table_create_ex", "mp_table_window_bits", "mp_table_destroy", "mp_shuffle_and_remask", "mp_verify_shuffle",
@@ -208,6 +208,8 @@ def bind(cdll):
     cdll.mp_set_plan_params.argtypes = [c.c_void_p, c.c_int] + [c.c_uint32] * 5
     cdll.mp_set_plan_thresholds.argtypes = [c.c_void_p] + [c.c_size_t] * 5
     cdll.mp_set_io_chunk.argtypes = [c.c_void_p, c.c_size_t]
+    cdll.mp_io_schedule.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.POINTER(c.c_size_t), c.c_size_t]
+    cdll.mp_io_schedule.restype = c.c_size_t
     cdll.mp_host_alloc.argtypes = [c.c_size_t]
     cdll.mp_host_alloc.restype = c.c_void_p
     cdll.mp_host_free.argtypes = [c.c_void_p]
@@ -950,6 +952,15 @@ class Table:
     def set_io_chunk(self, proofs):
         """proofs per pipelined chunk of the host-buffer entry points (0 = default 65536)"""
         self.eng._chk(self.lib.mp_set_io_chunk(self.h, proofs))
+
+    def io_schedule(self, B, verify=False):
+        """the chunk sizes, in order, that a host-buffer prove (verify=False) or verify call of B proofs takes under the current set_io_chunk"""
+        k = self.lib.mp_io_schedule(self.h, B, 1 if verify else 0, None, 0)
+        out = (ctypes.c_size_t * max(k, 1))()
+        k2 = self.lib.mp_io_schedule(self.h, B, 1 if verify else 0, out, k)
+        if k2 != k:
+            raise NativeError(MP_ERR_INTERNAL, "mp_io_schedule: the schedule changed between two calls")
+        return list(out)[:k]
 
     def set_merged_verify(self, on=True):
         """verification strategy: merged screening pass first (default) or always equation by equation"""

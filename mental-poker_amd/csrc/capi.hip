@@ -773,6 +773,13 @@ static std::vector<size_t> io_schedule(size_t B, size_t C, bool tail_ramp = true
   v.push_back(r0);
   return v;
 }
+// the chunk size and the chunks of one host-buffer call: what prove_batch_host / verify_batch_host cut their batch with and what
+// mp_io_schedule reports
+static std::vector<size_t> io_chunks(const mp_table* t, size_t B, bool verify, size_t* chunk = nullptr) {
+  const size_t C = io_chunk_of(t, B);
+  if (chunk) *chunk = C;
+  return io_schedule(B, C, !verify);
+}
 static void io_events(mp_io_stage& st) {
   if (!st.up) {
     st.up = rt::event_create();
@@ -808,8 +815,8 @@ static int prove_batch_host(mp_table* t, size_t B, const uint8_t* keys, const ui
   MP_ENTER(t->ctx);
   rt::Stream s = t->ctx->stream, up = t->ctx->h2d, down = t->ctx->d2h;
   const size_t N = t->N, psz = proof_size_bytes(t->m, t->n, t->point_bytes), dsz = N * 2 * t->point_bytes;
-  const size_t chunk = io_chunk_of(t, B);
-  const std::vector<size_t> sched = io_schedule(B, chunk);
+  size_t chunk = 0;
+  const std::vector<size_t> sched = io_chunks(t, B, false, &chunk);
   std::vector<size_t> first(sched.size() + 1, 0);
   for (size_t k = 0; k < sched.size(); ++k) first[k + 1] = first[k] + sched[k];
   const size_t nchunks = sched.size();
@@ -866,8 +873,8 @@ static int verify_batch_host(mp_table* t, size_t B, const uint8_t* keys, const u
   NoPipeline nopipe(t);
   rt::Stream s = t->ctx->stream, up = t->ctx->h2d, down = t->ctx->d2h;
   const size_t N = t->N, psz = proof_size_bytes(t->m, t->n, t->point_bytes), dsz = N * 2 * t->point_bytes;
-  const size_t chunk = io_chunk_of(t, B);
-  const std::vector<size_t> sched = io_schedule(B, chunk, false);
+  size_t chunk = 0;
+  const std::vector<size_t> sched = io_chunks(t, B, true, &chunk);
   std::vector<size_t> first(sched.size() + 1, 0);
   for (size_t k = 0; k < sched.size(); ++k) first[k + 1] = first[k] + sched[k];
   const size_t nchunks = sched.size();
@@ -908,6 +915,18 @@ static int verify_batch_host(mp_table* t, size_t B, const uint8_t* keys, const u
   MP_CATCH
 }
 
+size_t mp_io_schedule(const mp_table* t, size_t B, int verify, size_t* out_chunks, size_t cap) {
+  if (!t || !B) return 0;
+  try {
+    std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);      // (mp_set_io_chunk on another thread writes io_chunk)
+    const std::vector<size_t> sched = io_chunks(t, B, verify != 0);
+    for (size_t k = 0; k < sched.size() && k < cap && out_chunks; ++k) out_chunks[k] = sched[k];
+    return sched.size();
+  } catch (const std::exception& e) {
+    fail(MP_ERR_INTERNAL, e.what());
+    return 0;
+  }
+}
 int mp_shuffle_and_remask_batch(mp_table* t, size_t B, const uint8_t* decks, const uint8_t* masking_factors,
                                 const uint32_t* permutations, const uint8_t* prover_seeds, uint8_t* out_decks,
                                 uint8_t* out_proofs, int32_t* status) {

@@ -137,7 +137,10 @@ def test_emulated_chunked_host_pipeline(emu, coracle):
     st = t.verify_shuffle_batch(args[0], ref[0], swapped)
     assert st[0] > 0 and st[1] > 0 and st[2:] == [0] * 3
     # a call of three chunks and more ramps up and down (C/8, 3C/8, C ..., 3C/8, C/8): 27 proofs in chunks of 8 = 1 3 8 8 3 1 + ragged 3
-    ins2 = [coracle.gen_inputs(cv, m, n, 900 + b % 3) for b in range(27)]
+    # (27 distinct inputs: with repeating ones a chunk that lands a period off would pass; tests/host_pipeline_cases.py goes further)
+    ins2 = [coracle.gen_inputs(cv, m, n, 900 + b) for b in range(27)]
+    for what in ("deck", "rho", "prover_seed"):
+        assert len({g[what] for g in ins2}) == 27
     args2 = (b"".join(g["deck"] for g in ins2), b"".join(g["rho"] for g in ins2), [v for g in ins2 for v in g["perm"]],
              b"".join(g["prover_seed"] for g in ins2))
     t.set_io_chunk(0)
