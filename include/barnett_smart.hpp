@@ -204,6 +204,37 @@ class DLCardsT {
       throw CardProtocolError(mp_last_error());
     return o;
   }
+  // The same for cards with different numbers of tokens (mp_reveal_ragged_batch, mp_unmask_ragged_batch): counts[c] tokens for card c,
+  // signers, seeds, tokens, proofs and status words in lane order -- those of card c follow those of card c - 1.
+  RevealedTokens compute_reveal_tokens(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const Parameters& pp, const PublicKey& shared_key,
+                                       const std::vector<PublicKey>& keys, const std::vector<std::array<uint8_t, 32>>& secret_keys,
+                                       const std::vector<MaskedCard>& cards, const std::vector<uint32_t>& signer,
+                                       const std::vector<uint32_t>& counts) {
+    const std::vector<uint32_t> first = ragged_first(counts, cards.size(), signer.size(), "compute_reveal_tokens");
+    if (keys.empty() || secret_keys.size() != keys.size() || rng_seeds.size() != signer.size())
+      throw CardProtocolError("compute_reveal_tokens: one seed per token, one secret per key");
+    bind(pp, shared_key);
+    RevealedTokens r{std::vector<RevealToken>(signer.size()), std::vector<ZKProofReveal>(signer.size()), std::vector<int32_t>(signer.size())};
+    if (mp_reveal_ragged_batch(table_, keys.size(), keys[0].data(), secret_keys[0].data(), cards.size(), cards[0].data(), first.data(),
+                               signer.data(), rng_seeds[0].data(), r.tokens[0].data(), r.proofs[0].data(), r.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return r;
+  }
+  OpenedCards open_cards(const Parameters& pp, const PublicKey& shared_key, const std::vector<PublicKey>& keys, const std::vector<MaskedCard>& cards,
+                         const std::vector<uint32_t>& signer, const std::vector<RevealToken>& tokens, const std::vector<ZKProofReveal>& proofs,
+                         const std::vector<PublicKey>& card_list, const std::vector<uint32_t>& counts) {
+    const std::vector<uint32_t> first = ragged_first(counts, cards.size(), signer.size(), "open_cards");
+    if (keys.empty() || tokens.size() != signer.size() || proofs.size() != signer.size())
+      throw CardProtocolError("open_cards: one token and one proof per signer");
+    bind(pp, shared_key);
+    OpenedCards o{std::vector<PublicKey>(cards.size()), std::vector<uint32_t>(cards.size()), std::vector<int32_t>(signer.size()),
+                  std::vector<int32_t>(cards.size())};
+    if (mp_unmask_ragged_batch(table_, keys.size(), keys[0].data(), cards.size(), cards[0].data(), first.data(), signer.data(), tokens[0].data(),
+                               proofs[0].data(), card_list.size(), card_list.empty() ? nullptr : card_list[0].data(), o.plaintexts[0].data(),
+                               o.index.data(), o.token_status.data(), o.card_status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return o;
+  }
 
   // Dealing and seating in batches (mpshuffle.h "dealing and seating"): mask / verify_mask / remask / verify_remask [REF mod.rs:182-298]
   // for the cards of many tables, and compute_aggregate_key [REF mod.rs:167-180] for many tables, in one call each.  Card i goes under
@@ -249,6 +280,20 @@ class DLCardsT {
     AggregateKeys a{std::vector<PublicKey>(tables), std::vector<int32_t>(keys.size()), std::vector<int32_t>(tables)};
     if (mp_aggregate_keys_batch(table_, tables, (uint32_t)players, keys[0].data(), proofs[0].data(), fs_init[0].data(), a.keys[0].data(),
                                 a.player_status.data(), a.table_status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return a;
+  }
+  // tables of different sizes (mp_aggregate_keys_ragged_batch): players[k] players at table k, the lanes of table k after those of k - 1
+  AggregateKeys compute_aggregate_keys(const Parameters& pp, const std::vector<uint32_t>& players, const std::vector<PublicKey>& keys,
+                                       const std::vector<ZKProofKeyOwnership>& proofs, const std::vector<std::array<uint8_t, 32>>& fs_init) {
+    const std::vector<uint32_t> first = ragged_first(players, players.size(), keys.size(), "compute_aggregate_keys");
+    if (proofs.size() != keys.size() || fs_init.size() != keys.size())
+      throw CardProtocolError("compute_aggregate_keys: one proof and one digest per player");
+    bind_any(pp, keys[0]);
+    const size_t tables = players.size();
+    AggregateKeys a{std::vector<PublicKey>(tables), std::vector<int32_t>(keys.size()), std::vector<int32_t>(tables)};
+    if (mp_aggregate_keys_ragged_batch(table_, tables, first.data(), keys[0].data(), proofs[0].data(), fs_init[0].data(), a.keys[0].data(),
+                                       a.player_status.data(), a.table_status.data()) != MP_OK)
       throw CardProtocolError(mp_last_error());
     return a;
   }
@@ -384,6 +429,48 @@ class DLCardsT {
     return status;
   }
 
+  // The shuffle chains of many tables, of different lengths, in one call (mp_verify_shuffle_chain_ragged): table t brings links + 1 decks
+  // (deck j + 1 the output of link j), one proof per link and its aggregate key.  -> per table the status words of its links, those of
+  // verify_shuffle_batch link by link.
+  struct Chain {
+    PublicKey shared_key;
+    std::vector<std::vector<MaskedCard>> decks;
+    std::vector<ZKProofShuffle> proofs;
+  };
+  std::vector<std::vector<int32_t>> verify_shuffle_chains(const Parameters& pp, const std::vector<Chain>& chains) {
+    const size_t N = (size_t)pp.m * pp.n, psz = mp_proof_size_curve(curve_, pp.m, pp.n);
+    if (chains.empty()) throw CardProtocolError("verify_shuffle_chains: at least one table");
+    std::vector<uint32_t> links;
+    std::vector<MaskedCard> decks;
+    std::vector<PublicKey> keys;
+    std::vector<uint8_t> pf;
+    for (const Chain& ch : chains) {
+      if (ch.proofs.empty() || ch.decks.size() != ch.proofs.size() + 1)
+        throw CardProtocolError("verify_shuffle_chains: a chain is at least one link: links + 1 decks and one proof per link");
+      links.push_back((uint32_t)ch.proofs.size());
+      for (const std::vector<MaskedCard>& d : ch.decks) {
+        if (d.size() != N) throw CardProtocolError("decks must have m*n entries and proofs their wire length");
+        decks.insert(decks.end(), d.begin(), d.end());
+      }
+      for (const ZKProofShuffle& p : ch.proofs) {
+        if (p.size() != psz) throw CardProtocolError("decks must have m*n entries and proofs their wire length");
+        pf.insert(pf.end(), p.begin(), p.end());
+        keys.push_back(ch.shared_key);
+      }
+    }
+    bind_any(pp, chains[0].shared_key);
+    std::vector<int32_t> status(keys.size());
+    if (mp_verify_shuffle_chain_ragged(table_, chains.size(), links.data(), keys[0].data(), decks[0].data(), pf.data(), status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    std::vector<std::vector<int32_t>> out;
+    size_t o = 0;
+    for (uint32_t n : links) {
+      out.emplace_back(status.begin() + o, status.begin() + o + n);
+      o += n;
+    }
+    return out;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
   mp_pool_table* pool_table() const { return ptable_; }      // NULL without a device list
 
@@ -410,6 +497,19 @@ class DLCardsT {
                              proofs[0].data(), status.data()) != MP_OK)
       throw CardProtocolError(mp_last_error());
     return status;
+  }
+  // the offsets array of the ragged calls: item c owns the lanes first[c] .. first[c+1] - 1
+  static std::vector<uint32_t> ragged_first(const std::vector<uint32_t>& counts, size_t items, size_t lanes, const char* who) {
+    std::vector<uint32_t> first(counts.size() + 1, 0);
+    uint64_t sum = 0;
+    bool ok = !counts.empty() && counts.size() == items;
+    for (size_t i = 0; i < counts.size(); ++i) {
+      ok = ok && counts[i] >= 1;
+      sum += counts[i];
+      first[i + 1] = (uint32_t)sum;
+    }
+    if (!ok || sum != lanes) throw CardProtocolError(std::string(who) + ": counts must name at least one lane for every item, and all of them");
+    return first;
   }
   // G of the parameters: the key of a table that is bound for calls that use no key
   static PublicKey generator(const Parameters& pp) {

@@ -218,6 +218,16 @@ int mp_verify_shuffle_chain(mp_table* t, size_t tables, uint32_t links, const ui
                             const uint8_t* proofs, int32_t* status);
 int mp_verify_shuffle_chain_dev(mp_table* t, size_t tables, uint32_t links, const void* d_keys, const void* d_decks, const void* d_proofs,
                                 void* d_status);
+/* mp_verify_shuffle_chain_ragged: the tables of one call may have chains of different lengths, links[t] >= 1 links for table t (host
+ * buffers only).  The layout is table-major -- link-major needs equal lengths: with off(t) = links[0] + ... + links[t-1], table t owns
+ * the decks off(t) + t .. off(t) + t + links[t] (consecutive: deck j + 1 is the output of link j) and the proofs, status words and keys
+ * off(t) .. off(t) + links[t] - 1 (keys: one per link; NULL = the mp_table's own key).  The tables are grouped by links[t]; each group is
+ * gathered on the host into the link-major arrays above and verified by one mp_verify_shuffle_chain call; once every group has been
+ * verified the status words are scattered back (on a return other than MP_OK the status array is as it was):
+ * mp_set_chain_group, _max_links and _slice apply to each group as to a call of that group alone, and the status words are those of
+ * mp_verify_shuffle_batch[_keys] link by link.  tables == 0, a links[t] of 0 or above 4 095, or 2^31 proofs and more: MP_ERR_BAD_ARGUMENT. */
+int mp_verify_shuffle_chain_ragged(mp_table* t, size_t tables, const uint32_t* links, const uint8_t* shared_keys, const uint8_t* decks,
+                                   const uint8_t* proofs, int32_t* status);
 int mp_sync(mp_ctx* ctx);
 int mp_reserve(mp_table* t, size_t B);           /* pre-allocate the batch workspace for B proofs */
 /* Every table holds six static work splits with identical results: a throughput plan (large sub-jobs, fewest operations) and five
@@ -481,6 +491,25 @@ int mp_unmask_batch(mp_table* t, size_t K, const uint8_t* keys, size_t C, const 
 int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, const void* d_cards, uint32_t T, const void* d_signer,
                         const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards, void* d_out_plain,
                         void* d_out_index, void* d_token_status, void* d_card_status);
+/* The same three calls for cards with DIFFERENT numbers of tokens (tables of 2 to 10 seats in one call): instead of T an offsets array
+ *   first    C + 1 uint32: card c owns the lanes first[c] .. first[c+1] - 1; first[0] == 0, strictly increasing (every card has at
+ *   least one token), first[C] <= 1 048 576 = the number of lanes of the call.
+ * Everything per token -- signer, tokens, proofs, prover_seeds, status words -- comes in lane order.  `first` is ALWAYS a host array, in
+ * the _dev form too: the library copies it, validates the copy on the host and uploads THAT into a buffer the table keeps, so a
+ * malformed array is MP_ERR_BAD_ARGUMENT for the call with nothing enqueued and no buffer touched, never an index out of range on the
+ * device; the caller's array -- pageable or page-locked -- is consumed before the call returns.  Everything else is what the uniform calls promise, per card: the status words, zero bytes for
+ * lanes and cards that fail, card_status[c] = the first token status of the card that is not 0 in lane order, out_index, the validation of
+ * the card list, the subgroup checks, mp_set_sigma_screen, the other limits; never coalesced.  With first[c] = c * T the outputs are
+ * the bytes and words of the uniform call. */
+int mp_reveal_ragged_batch(mp_table* t, size_t K, const uint8_t* keys, const uint8_t* secret_keys, size_t C, const uint8_t* cards,
+                           const uint32_t* first, const uint32_t* signer, const uint8_t* prover_seeds, uint8_t* out_tokens,
+                           uint8_t* out_proofs, int32_t* status);
+int mp_unmask_ragged_batch(mp_table* t, size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, const uint32_t* first,
+                           const uint32_t* signer, const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain_cards,
+                           uint8_t* out_plain, uint32_t* out_index, int32_t* token_status, int32_t* card_status);
+int mp_unmask_ragged_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, const void* d_cards, const uint32_t* first,
+                               const void* d_signer, const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards,
+                               void* d_out_plain, void* d_out_index, void* d_token_status, void* d_card_status);
 
 /* ---- dealing and seating in batches: masking / remasking with their proofs, and the tables' aggregate keys
  * [REF mod.rs:151-298; examples/round.rs:228-262]
@@ -521,6 +550,11 @@ int mp_verify_mask_batch_dev(mp_table* t, int kind, size_t K, const void* d_keys
                              const void* d_masked, const void* d_proofs, void* d_status);
 int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                             uint8_t* out_keys, int32_t* player_status, int32_t* table_status);
+/* mp_aggregate_keys_ragged_batch: tables of different sizes in one call.  first: tables + 1 uint32 offsets (a host array, with the rules
+ * of mp_unmask_ragged_batch's): table k seats the lanes first[k] .. first[k+1] - 1, at least one, first[tables] <= 1 048 576 lanes in all.
+ * Everything else as mp_aggregate_keys_batch, per table; with first[k] = k * P the outputs are its bytes and words. */
+int mp_aggregate_keys_ragged_batch(mp_table* t, size_t tables, const uint32_t* first, const uint8_t* keys, const uint8_t* proofs,
+                                   const uint8_t* fs_init, uint8_t* out_keys, int32_t* player_status, int32_t* table_status);
 
 /* ---- secrets drawn on the device from seeds: shuffle witnesses and player keys
  * [REF examples/round.rs:265-266, examples/parameter_selection.rs:38-39, mod.rs:123-130: Fr::rand(rng) / sample_vector(rng, N), then
@@ -563,7 +597,8 @@ int mp_keygen_batch(mp_table* t, size_t K, const uint8_t* seeds, const uint8_t* 
                     uint8_t* out_proofs, int32_t* status);
 
 /* ---- screening the sigma verifiers with grouped bucket equations (opt-in, off by default) -------------------------------------------
- * mp_unmask_batch[_dev], mp_verify_mask_batch[_dev], mp_aggregate_keys_batch and mp_sigma_verify_batch check every proof on a plan of its
+ * mp_unmask_batch[_dev], mp_verify_mask_batch[_dev], mp_aggregate_keys_batch and mp_sigma_verify_batch (and the ragged forms of the first
+ * and the third, whose groups of consecutive lanes do not care where a card or a table ends) check every proof on a plan of its
  * own: per lane about 3 x (51 + 15) additions and 500 doublings.  With the screen on, the checks z g_i - c a_i - A_i = O of a GROUP of
  * consecutive lanes are added up -- each check with a weight of its own, two per Chaum-Pedersen lane, one per Schnorr lane -- into ONE
  * multi-scalar multiplication on the bucket pipeline of the shuffle verifier (a lane is five points of it where one base is the table's

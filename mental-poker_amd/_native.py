@@ -28,6 +28,8 @@ SYMBOLS = [
     "mp_sigma_verify_batch", "mp_blake2s", "mp_reveal_batch", "mp_unmask_batch", "mp_unmask_batch_dev",
     "mp_mask_batch", "mp_verify_mask_batch", "mp_verify_mask_batch_dev", "mp_aggregate_keys_batch",
     "mp_set_sigma_screen", "mp_sigma_screen_stats",
+    "mp_reveal_ragged_batch", "mp_unmask_ragged_batch", "mp_unmask_ragged_batch_dev", "mp_aggregate_keys_ragged_batch",
+    "mp_verify_shuffle_chain_ragged",
     "mp_sample_secrets_batch", "mp_sample_secrets_batch_dev", "mp_shuffle_and_remask_batch_seeded", "mp_shuffle_and_remask_batch_seeded_dev",
     "mp_keygen_batch",
     "mp_pool_create", "mp_pool_destroy", "mp_pool_size", "mp_pool_member_ctx", "mp_pool_table_create", "mp_pool_table_destroy",
@@ -251,6 +253,7 @@ def bind(cdll):
     cdll.mp_verify_shuffle_batch_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
     cdll.mp_verify_shuffle_chain.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, i32p]
     cdll.mp_verify_shuffle_chain_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32] + [c.c_void_p] * 4
+    cdll.mp_verify_shuffle_chain_ragged.argtypes = [c.c_void_p, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_sync.argtypes = [c.c_void_p]
     cdll.mp_reserve.argtypes = [c.c_void_p, c.c_size_t]
     cdll.mp_set_latency_batch.argtypes = [c.c_void_p, c.c_size_t]
@@ -267,6 +270,10 @@ def bind(cdll):
     cdll.mp_reveal_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_unmask_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, c.c_size_t, u8p, c.c_uint32, u32p, u8p, u8p, c.c_size_t, u8p, u8p, u32p, i32p, i32p]
     cdll.mp_unmask_batch_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint32] + [c.c_void_p] * 3 + [c.c_size_t] + [c.c_void_p] * 5
+    cdll.mp_reveal_ragged_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, u8p, c.c_size_t, u8p, u32p, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_unmask_ragged_batch.argtypes = [c.c_void_p, c.c_size_t, u8p, c.c_size_t, u8p, u32p, u32p, u8p, u8p, c.c_size_t, u8p, u8p, u32p, i32p, i32p]
+    cdll.mp_unmask_ragged_batch_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, u32p] + [c.c_void_p] * 3 + [c.c_size_t] + [c.c_void_p] * 5
+    cdll.mp_aggregate_keys_ragged_batch.argtypes = [c.c_void_p, c.c_size_t, u32p, u8p, u8p, u8p, u8p, i32p, i32p]
     cdll.mp_mask_batch.argtypes = [c.c_void_p, c.c_int, c.c_size_t, u8p, c.c_size_t, u32p, u8p, u8p, u8p, u8p, u8p, i32p]
     cdll.mp_verify_mask_batch.argtypes = [c.c_void_p, c.c_int, c.c_size_t, u8p, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
     cdll.mp_verify_mask_batch_dev.argtypes = [c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
@@ -671,6 +678,20 @@ class Table:
                                                        _in(proofs), st))
         return list(st)
 
+    def verify_shuffle_chain_ragged(self, links, decks, proofs, keys=None):
+        """chains of different lengths: links[t] shuffles for table t, table-major -- table t owns the decks off(t) + t .. off(t) + t +
+        links[t] and the proofs, keys and status words off(t) .. off(t) + links[t] - 1, off(t) = sum(links[:t]) -> status words"""
+        tables, total = len(links), sum(links)
+        self._need("decks", len(decks), (total + tables) * self.N * self.cb)
+        self._need("proofs", len(proofs), total * self.proof_bytes)
+        if keys is not None:
+            self._need("keys", len(keys), total * self.pb)
+        st = (ctypes.c_int32 * max(total, 1))()
+        lk = (ctypes.c_uint32 * max(tables, 1))(*links)
+        self.eng._chk(self.lib.mp_verify_shuffle_chain_ragged(self.h, tables, lk, _in(keys) if keys is not None else None, _in(decks),
+                                                              _in(proofs), st))
+        return list(st)[:total]
+
     def verify_shuffle_chain_dev(self, tables, links, d_keys, d_decks, d_proofs, d_status):
         self.eng._chk(self.lib.mp_verify_shuffle_chain_dev(self.h, tables, links, d_keys, d_decks, d_proofs, d_status))
 
@@ -848,6 +869,76 @@ class Table:
         """the same with device pointers (d_cards may be the prover's d_out_decks); outputs are final after Engine.sync()"""
         self.eng._chk(self.lib.mp_unmask_batch_dev(self.h, K, d_keys, C, d_cards, T, d_signer, d_tokens, d_proofs, n_plain, d_plain_cards,
                                                    d_out_plain, d_out_index, d_token_status, d_card_status))
+
+    # ---- the same for cards with different numbers of tokens: counts[c] tokens for card c, everything per token in lane order
+    @staticmethod
+    def ragged_first(counts):
+        """the offsets array of the ragged calls: item c owns the lanes first[c] .. first[c+1] - 1"""
+        first = (ctypes.c_uint32 * (len(counts) + 1))()
+        for i, n in enumerate(counts):
+            first[i + 1] = first[i] + n
+        return first
+
+    def reveal_ragged_batch(self, keys, secret_keys, cards, counts, signer, seeds):
+        """reveal_batch with counts[c] tokens for card c -> (tokens, proofs, status)"""
+        K, C = len(keys) // self.pb, len(cards) // self.cb
+        B = sum(counts)
+        self._need("keys", len(keys), K * self.pb)
+        self._need("secret keys", len(secret_keys), K * 32)
+        self._need("cards", len(cards), C * self.cb)
+        self._need("counts", len(counts), C)
+        self._need("signer", len(signer), B)
+        self._need("prover seeds", len(seeds), B * 32)
+        tok = (ctypes.c_uint8 * max(B * self.pb, 1))()
+        prf = (ctypes.c_uint8 * max(B * (2 * self.pb + 32), 1))()
+        st = (ctypes.c_int32 * max(B, 1))()
+        sg = (ctypes.c_uint32 * max(B, 1))(*signer)
+        self.eng._chk(self.lib.mp_reveal_ragged_batch(self.h, K, _in(keys), _in(secret_keys), C, _in(cards), self.ragged_first(counts), sg,
+                                                      _in(seeds), tok, prf, st))
+        return bytes(tok)[:B * self.pb], bytes(prf)[:B * (2 * self.pb + 32)], list(st)[:B]
+
+    def unmask_ragged_batch(self, keys, cards, counts, signer, tokens, proofs, plain_cards=b""):
+        """unmask_batch with counts[c] tokens for card c -> (plaintexts, indices, token_status, card_status)"""
+        K, C = len(keys) // self.pb, len(cards) // self.cb
+        B = sum(counts)
+        n_plain = len(plain_cards) // self.pb
+        self._need("keys", len(keys), K * self.pb)
+        self._need("cards", len(cards), C * self.cb)
+        self._need("counts", len(counts), C)
+        self._need("signer", len(signer), B)
+        self._need("tokens", len(tokens), B * self.pb)
+        self._need("proofs", len(proofs), B * (2 * self.pb + 32))
+        self._need("card list", len(plain_cards), n_plain * self.pb)
+        out = (ctypes.c_uint8 * max(C * self.pb, 1))()
+        idx = (ctypes.c_uint32 * max(C, 1))()
+        ts = (ctypes.c_int32 * max(B, 1))()
+        cs = (ctypes.c_int32 * max(C, 1))()
+        sg = (ctypes.c_uint32 * max(B, 1))(*signer)
+        self.eng._chk(self.lib.mp_unmask_ragged_batch(self.h, K, _in(keys), C, _in(cards), self.ragged_first(counts), sg, _in(tokens),
+                                                      _in(proofs), n_plain, _in(plain_cards) if n_plain else None, out, idx, ts, cs))
+        return bytes(out)[:C * self.pb], list(idx)[:C], list(ts)[:B], list(cs)[:C]
+
+    def unmask_ragged_batch_dev(self, K, d_keys, counts, d_cards, d_signer, d_tokens, d_proofs, n_plain, d_plain_cards, d_out_plain,
+                                d_out_index, d_token_status, d_card_status):
+        """the same with device pointers; `counts` stays a host list (the offsets are validated on the host and uploaded by the
+        library before the call returns); outputs are final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_unmask_ragged_batch_dev(self.h, K, d_keys, len(counts), d_cards, self.ragged_first(counts), d_signer,
+                                                          d_tokens, d_proofs, n_plain, d_plain_cards, d_out_plain, d_out_index,
+                                                          d_token_status, d_card_status))
+
+    def aggregate_keys_ragged_batch(self, counts, keys, proofs, fs_init):
+        """seating tables of different sizes: counts[k] players at table k, lanes in table order
+        -> (aggregate keys, player status, table status)"""
+        tables, B = len(counts), sum(counts)
+        self._need("keys", len(keys), B * self.pb)
+        self._need("proofs", len(proofs), B * (self.pb + 32))
+        self._need("fs_init", len(fs_init), B * 32)
+        out = (ctypes.c_uint8 * max(tables * self.pb, 1))()
+        ps = (ctypes.c_int32 * max(B, 1))()
+        ts = (ctypes.c_int32 * max(tables, 1))()
+        self.eng._chk(self.lib.mp_aggregate_keys_ragged_batch(self.h, tables, self.ragged_first(counts), _in(keys), _in(proofs),
+                                                              _in(fs_init), out, ps, ts))
+        return bytes(out)[:tables * self.pb], list(ps)[:B], list(ts)[:tables]
 
     # ---- dealing and seating: K aggregate keys, C cards with a key index each; kind: DEAL_MASK (inputs = plaintext cards, one point
     #      each) or DEAL_REMASK (inputs = masked cards)

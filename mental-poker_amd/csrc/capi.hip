@@ -265,6 +265,13 @@ void mp_table_destroy(mp_table* t) {
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     auto& reg = ctx->tables;
     reg.erase(std::remove(reg.begin(), reg.end(), t), reg.end());
+    if (t->ragged_first_up) {
+      try {
+        rt::event_sync(t->ragged_first_up);
+      } catch (...) {
+      }
+      rt::event_destroy(t->ragged_first_up);
+    }
     for (auto& st : t->io) {
       if (st.up) rt::event_destroy(st.up);
       if (st.done) rt::event_destroy(st.done);
@@ -702,6 +709,60 @@ int mp_verify_shuffle_chain(mp_table* t, size_t tables, uint32_t links, const ui
   if (rc != MP_OK) return rc;
   rt::d2h(status, ds.p, B * 4, s);
   rt::stream_sync(s);
+  return MP_OK;
+  MP_CATCH
+}
+// Chains of different lengths: the tables are grouped by their number of links, each group is gathered from the table-major arrays of the
+// caller into the link-major arrays of mp_verify_shuffle_chain, verified as a call of that group alone, and its words are scattered back.
+int mp_verify_shuffle_chain_ragged(mp_table* t, size_t tables, const uint32_t* links, const uint8_t* shared_keys, const uint8_t* decks,
+                                   const uint8_t* proofs, int32_t* status) {
+  if (!t || !tables || !links || !decks || !proofs || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: bad argument");
+  std::vector<size_t> off(tables + 1, 0);
+  for (size_t k = 0; k < tables; ++k) {
+    if (links[k] < 1 || links[k] > 4095) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: 1 <= links[t] <= 4 095 for every table");
+    off[k + 1] = off[k] + links[k];
+  }
+  if ((uint64_t)off[tables] >= ((uint64_t)1 << 31)) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: too many proofs for one call");
+  if (t->keyless && !shared_keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: pass one key per link");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  const size_t pb = t->point_bytes, deck_bytes = (size_t)2 * t->N * pb, psz = proof_size_bytes(t->m, t->n, (uint32_t)pb);
+  std::vector<size_t> order(tables);
+  for (size_t k = 0; k < tables; ++k) order[k] = k;
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return links[a] < links[b]; });
+  // staging for one group at a time, sized once for the largest group and not zero-filled; the words of every group are kept until all
+  // groups have been verified, so that a call that fails half way leaves the caller's status array as it was
+  size_t max_d = 0, max_p = 0;
+  for (size_t i0 = 0; i0 < tables;) {
+    const uint32_t L = links[order[i0]];
+    size_t i1 = i0;
+    while (i1 < tables && links[order[i1]] == L) ++i1;
+    max_d = std::max(max_d, (size_t)(L + 1) * (i1 - i0));
+    max_p = std::max(max_p, (size_t)L * (i1 - i0));
+    i0 = i1;
+  }
+  std::unique_ptr<uint8_t[]> gd(new uint8_t[max_d * deck_bytes]), gp(new uint8_t[max_p * psz]), gk(new uint8_t[shared_keys ? max_p * pb : 1]);
+  std::vector<int32_t> gs(max_p), words(off[tables]);
+  for (size_t i0 = 0; i0 < tables;) {
+    const uint32_t L = links[order[i0]];
+    size_t i1 = i0;
+    while (i1 < tables && links[order[i1]] == L) ++i1;
+    const size_t G = i1 - i0;
+    for (size_t g = 0; g < G; ++g) {
+      const size_t k = order[i0 + g], o = off[k];
+      for (uint32_t j = 0; j <= L; ++j) memcpy(gd.get() + ((size_t)j * G + g) * deck_bytes, decks + (o + k + j) * deck_bytes, deck_bytes);
+      for (uint32_t j = 0; j < L; ++j) {
+        memcpy(gp.get() + ((size_t)j * G + g) * psz, proofs + (o + j) * psz, psz);
+        if (shared_keys) memcpy(gk.get() + ((size_t)j * G + g) * pb, shared_keys + (o + j) * pb, pb);
+      }
+    }
+    const int rc = mp_verify_shuffle_chain(t, G, L, shared_keys ? gk.get() : nullptr, gd.get(), gp.get(), gs.data());
+    if (rc != MP_OK) return rc;
+    for (size_t g = 0; g < G; ++g)
+      for (uint32_t j = 0; j < L; ++j) words[off[order[i0 + g]] + j] = gs[(size_t)j * G + g];
+    i0 = i1;
+  }
+  memcpy(status, words.data(), words.size() * sizeof(int32_t));
   return MP_OK;
   MP_CATCH
 }
@@ -1279,6 +1340,31 @@ static const size_t OPEN_MAX_LANES = 1048576, OPEN_MAX_KEYS = 1048576, OPEN_MAX_
 static bool open_shape_ok(size_t K, size_t C, uint32_t T) {
   return K >= 1 && K <= OPEN_MAX_KEYS && C >= 1 && C <= OPEN_MAX_LANES && T >= 1 && T <= OPEN_MAX_LANES && C * (size_t)T <= OPEN_MAX_LANES;
 }
+// The offsets array of the ragged calls, a host array: C + 1 entries, first[0] = 0, strictly increasing, first[C] <= max_lanes.  The
+// caller's array is copied into a vector the table keeps and checked THERE, before anything is enqueued, and the device copy is made from
+// that vector: no kernel ever sees an offset that was not validated, the caller may do what it likes with its array once the call has
+// returned, and it does not matter whether the array is pageable or page-locked (a copy from page-locked memory is only queued when
+// hipMemcpyAsync returns).  The vector is not touched again before the event behind its upload has passed.  Holds the context's lock.
+// -> the device array, or nullptr for a malformed one
+static const uint32_t* ragged_take(mp_table* t, size_t count, const uint32_t* first, size_t max_lanes) {
+  if (count < 1 || count > max_lanes) return nullptr;
+  rt::Stream s = t->ctx->stream;
+  if (t->ragged_first_up)
+    rt::event_sync(t->ragged_first_up);
+  else
+    t->ragged_first_up = rt::event_create();
+  std::vector<uint32_t>& h = t->ragged_first_host;
+  h.assign(first, first + count + 1);
+  if (h[0] != 0 || h[count] > max_lanes) return nullptr;
+  for (size_t c = 0; c < count; ++c)
+    if (h[c + 1] <= h[c]) return nullptr;
+  t->ragged_first.alloc(count + 1, s, false);
+  rt::h2d(t->ragged_first.p, h.data(), (count + 1) * 4, s);
+  rt::event_record(t->ragged_first_up, s);
+  return t->ragged_first.p;
+}
+static const char* const RAGGED_SHAPE =
+    "first[0] == 0, first strictly increasing, first[C] <= 1 048 576, 1 <= K <= 1 048 576, n_plain <= 4 096";
 int mp_reveal_batch(mp_table* t, size_t K, const uint8_t* keys, const uint8_t* secret_keys, size_t C, const uint8_t* cards, uint32_t T,
                     const uint32_t* signer, const uint8_t* prover_seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) {
   if (!t || !keys || !secret_keys || !cards || !signer || !prover_seeds || !out_tokens || !out_proofs || !status)
@@ -1315,6 +1401,48 @@ int mp_unmask_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, con
   return t->unmask_dev(K, (const uint8_t*)d_keys, C, (const uint8_t*)d_cards, T, (const uint32_t*)d_signer, (const uint8_t*)d_tokens,
                        (const uint8_t*)d_proofs, n_plain, (const uint8_t*)d_plain_cards, (uint8_t*)d_out_plain, (uint32_t*)d_out_index,
                        (int32_t*)d_token_status, (int32_t*)d_card_status);
+  MP_CATCH
+}
+int mp_reveal_ragged_batch(mp_table* t, size_t K, const uint8_t* keys, const uint8_t* secret_keys, size_t C, const uint8_t* cards,
+                           const uint32_t* first, const uint32_t* signer, const uint8_t* prover_seeds, uint8_t* out_tokens,
+                           uint8_t* out_proofs, int32_t* status) {
+  if (!t || !keys || !secret_keys || !cards || !first || !signer || !prover_seeds || !out_tokens || !out_proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_reveal_ragged_batch: null argument");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  const uint32_t* d_first = K >= 1 && K <= OPEN_MAX_KEYS ? ragged_take(t, C, first, OPEN_MAX_LANES) : nullptr;
+  if (!d_first) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_reveal_ragged_batch: ") + RAGGED_SHAPE);
+  t->reveal_host(K, keys, secret_keys, C, cards, 0, signer, prover_seeds, out_tokens, out_proofs, status, d_first, t->ragged_first_host[C]);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_unmask_ragged_batch(mp_table* t, size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, const uint32_t* first,
+                           const uint32_t* signer, const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain_cards,
+                           uint8_t* out_plain, uint32_t* out_index, int32_t* token_status, int32_t* card_status) {
+  if (!t || !keys || !cards || !first || !signer || !tokens || !proofs || (n_plain && !plain_cards) || !out_plain || !out_index || !token_status ||
+      !card_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_ragged_batch: null argument");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  const uint32_t* d_first = K >= 1 && K <= OPEN_MAX_KEYS && n_plain <= OPEN_MAX_CARD_LIST ? ragged_take(t, C, first, OPEN_MAX_LANES) : nullptr;
+  if (!d_first) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_unmask_ragged_batch: ") + RAGGED_SHAPE);
+  return t->unmask_host(K, keys, C, cards, 0, signer, tokens, proofs, n_plain, plain_cards, out_plain, out_index, token_status, card_status,
+                        d_first, t->ragged_first_host[C]);
+  MP_CATCH
+}
+int mp_unmask_ragged_batch_dev(mp_table* t, size_t K, const void* d_keys, size_t C, const void* d_cards, const uint32_t* first,
+                               const void* d_signer, const void* d_tokens, const void* d_proofs, size_t n_plain, const void* d_plain_cards,
+                               void* d_out_plain, void* d_out_index, void* d_token_status, void* d_card_status) {
+  if (!t || !d_keys || !d_cards || !first || !d_signer || !d_tokens || !d_proofs || (n_plain && !d_plain_cards) || !d_out_plain || !d_out_index ||
+      !d_token_status || !d_card_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_unmask_ragged_batch_dev: null argument");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  const uint32_t* d_first = K >= 1 && K <= OPEN_MAX_KEYS && n_plain <= OPEN_MAX_CARD_LIST ? ragged_take(t, C, first, OPEN_MAX_LANES) : nullptr;
+  if (!d_first) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_unmask_ragged_batch_dev: ") + RAGGED_SHAPE);
+  return t->unmask_dev(K, (const uint8_t*)d_keys, C, (const uint8_t*)d_cards, 0, (const uint32_t*)d_signer, (const uint8_t*)d_tokens,
+                       (const uint8_t*)d_proofs, n_plain, (const uint8_t*)d_plain_cards, (uint8_t*)d_out_plain, (uint32_t*)d_out_index,
+                       (int32_t*)d_token_status, (int32_t*)d_card_status, false, d_first, t->ragged_first_host[C]);
   MP_CATCH
 }
 
@@ -1366,6 +1494,19 @@ int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_
   MP_TRY
   MP_ENTER(t->ctx);
   t->aggregate_keys_host(tables, P, keys, proofs, fs_init, out_keys, player_status, table_status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_aggregate_keys_ragged_batch(mp_table* t, size_t tables, const uint32_t* first, const uint8_t* keys, const uint8_t* proofs,
+                                   const uint8_t* fs_init, uint8_t* out_keys, int32_t* player_status, int32_t* table_status) {
+  if (!t || !first || !keys || !proofs || !fs_init || !out_keys || !player_status || !table_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_aggregate_keys_ragged_batch: null argument");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  const uint32_t* d_first = ragged_take(t, tables, first, DEAL_MAX_LANES);
+  if (!d_first)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_aggregate_keys_ragged_batch: first[0] == 0, first strictly increasing, first[tables] <= 1 048 576");
+  t->aggregate_keys_host(tables, 0, keys, proofs, fs_init, out_keys, player_status, table_status, d_first, t->ragged_first_host[tables]);
   return MP_OK;
   MP_CATCH
 }

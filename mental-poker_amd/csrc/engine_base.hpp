@@ -279,15 +279,20 @@ struct mp_table {
   virtual void sigma_host(bool prove, size_t B, uint32_t nb, const uint8_t* bases, const uint8_t* publics, const uint8_t* witness,
                           const uint8_t* fs_init, const uint8_t* seeds, uint8_t* proofs, int32_t* status) = 0;
   // opening cards (kernels_open.hpp): K keys, C cards, T tokens per card, lane c * T + j; reveal_host / unmask_host take host
-  // buffers, unmask_dev device pointers.  unmask_*: MP_OK, or MP_ERR_BAD_ENCODING for a bad entry of the card list
+  // buffers, unmask_dev device pointers.  unmask_*: MP_OK, or MP_ERR_BAD_ENCODING for a bad entry of the card list.
+  // With `first` (device memory, [C + 1] offsets that the C ABI has validated; `lanes` = first[C]) card c owns the lanes
+  // first[c] .. first[c+1] - 1 and T is not read; the same for the tables of aggregate_keys_host
   virtual void reveal_host(size_t K, const uint8_t* keys, const uint8_t* sks, size_t C, const uint8_t* cards, uint32_t T,
-                           const uint32_t* signer, const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) = 0;
+                           const uint32_t* signer, const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status,
+                           const uint32_t* first = nullptr, size_t lanes = 0) = 0;
   virtual int unmask_host(size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
                           const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain,
-                          uint32_t* out_index, int32_t* token_status, int32_t* card_status) = 0;
+                          uint32_t* out_index, int32_t* token_status, int32_t* card_status, const uint32_t* first = nullptr,
+                          size_t lanes = 0) = 0;
   virtual int unmask_dev(size_t K, const uint8_t* keys, size_t C, const uint8_t* cards, uint32_t T, const uint32_t* signer,
                          const uint8_t* tokens, const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain,
-                         uint32_t* out_index, int32_t* token_status, int32_t* card_status, bool plain_validated = false) = 0;
+                         uint32_t* out_index, int32_t* token_status, int32_t* card_status, bool plain_validated = false,
+                         const uint32_t* first = nullptr, size_t lanes = 0) = 0;
   // dealing and seating (kernels_deal.hpp): K keys, C cards with a key index each, kind = MP_DEAL_MASK | MP_DEAL_REMASK; mask_host /
   // verify_mask_host / aggregate_keys_host take host buffers, verify_mask_dev device pointers
   virtual void mask_host(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
@@ -297,7 +302,15 @@ struct mp_table {
   virtual void verify_mask_dev(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
   virtual void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
-                                   uint8_t* out_keys, int32_t* player_status, int32_t* table_status) = 0;
+                                   uint8_t* out_keys, int32_t* player_status, int32_t* table_status, const uint32_t* first = nullptr,
+                                   size_t lanes = 0) = 0;
+  // the offsets array of the ragged calls (capi.hip ragged_take): the caller's array is copied into ragged_first_host, validated THERE and
+  // uploaded from there into ragged_first, so what the kernels read is what was validated whatever the caller does with its array
+  // after the call returns, and whatever kind of memory it lies in.  ragged_first_up is recorded behind the upload: the host copy is not
+  // overwritten (by the next ragged call) or freed (mp_table_destroy) before that copy has been made
+  mp::DevBuf<uint32_t> ragged_first;
+  std::vector<uint32_t> ragged_first_host;
+  mp::rt::Event ragged_first_up = nullptr;
   // secrets from seeds (kernels_sample.hpp, "mpshuffle secret stream v1"): L seeds -> S wire scalars and a permutation of length P each;
   // sample_dev takes device pointers and is enqueued on the context's stream, sample_host host buffers.  keygen_host: sk = the stream's
   // single scalar, pk = sk G, and with fs_init the Schnorr proof of key ownership under the prover seed seeds[k]

@@ -2350,7 +2350,7 @@ struct Table : mp_table {
 
   // ---------------------------------------------------------------- opening cards (kernels_open.hpp)
   // Reveal tokens with their Chaum-Pedersen proofs, and their verification with the token sums and the card lookup, for the T tokens
-  // of C cards at once: lane b = c * T + j, the statement slots of kernels_sigma.hpp filled on the device (k_open_stmt).  Against
+  // of C cards at once: lane b = c * T + j (or, with an offsets array, the lanes first[c] .. first[c+1] - 1), the statement slots of kernels_sigma.hpp filled on the device (k_open_stmt).  Against
   // sigma_host, which knows nothing about its statements: G is the table's fixed base (window table in HBM, no doubling chain), the
   // commitments enter the checks as affine addends instead of terms with the scalar -1, and the prover builds the window table of c0
   // once for token and commitment.  The plans are static and the workspace stays with the table: a device-resident call allocates
@@ -2428,7 +2428,8 @@ struct Table : mp_table {
     op.fs.alloc((size_t)op.w.cap * 32, s, false);
     rt::dzero(op.w.status.p, (size_t)op.w.Bpad * 4, s);
   }
-  OpenStmtArgs open_stmt_args(size_t K, const uint8_t* keys, const uint8_t* cards, uint32_t T, const uint32_t* signer) {
+  OpenStmtArgs open_stmt_args(size_t K, const uint8_t* keys, const uint8_t* cards, uint32_t T, const uint32_t* signer, const uint32_t* first,
+                              size_t C_) {
     OpenStmtArgs a{};
     Workspace& w = op.w;
     a.P = w.P.p; a.S = w.S.p; a.status = w.status.p;
@@ -2438,6 +2439,7 @@ struct Table : mp_table {
     memcpy(a.fs_seed, op.fs_seed, 32);
     a.l = make_sigma_lay(2);
     a.Bpad = w.Bpad; a.K = (uint32_t)K; a.T = T; a.g_base = FixedBases{n}.G();
+    a.first = first; a.C = (uint32_t)C_;
     return a;
   }
   int check_card_list(size_t n_plain, const uint8_t* plain) {
@@ -2453,9 +2455,9 @@ struct Table : mp_table {
   // tested for the subgroup.)
   int unmask_dev(size_t K, const uint8_t* keys, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer, const uint8_t* tokens,
                  const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain, uint32_t* out_index,
-                 int32_t* token_status, int32_t* card_status, bool plain_validated) override {
+                 int32_t* token_status, int32_t* card_status, bool plain_validated, const uint32_t* first, size_t lanes) override {
     rt::Stream s = ctx->stream;
-    const uint32_t Cn = (uint32_t)C_, B = Cn * T;
+    const uint32_t Cn = (uint32_t)C_, B = first ? (uint32_t)lanes : Cn * T;
     if (n_plain && !plain_validated) {
       std::vector<uint8_t> hp(n_plain * G_::PB);
       rt::d2h(hp.data(), plain, hp.size(), s);
@@ -2469,7 +2471,7 @@ struct Table : mp_table {
     op.c1.alloc((size_t)Cn * G_::PW, s, false); op.sumJ.alloc((size_t)Cn * G_::JW, s, false); op.sumP.alloc((size_t)Cn * G_::PW, s, false);
     op.scratch.alloc((size_t)Cn * G_::FW, s, false); op.cstat.alloc(Cn, s, false);
     rt::dzero(op.cstat.p, (size_t)Cn * 4, s);
-    OpenStmtArgs sa = open_stmt_args(K, keys, cards, T, signer);
+    OpenStmtArgs sa = open_stmt_args(K, keys, cards, T, signer, first, C_);
     sa.tokens = tokens; sa.c1 = op.c1.p; sa.cstat = op.cstat.p;
     MP_RUN(k_open_stmt, C, B, 4, sa);
     SigmaIoArgs io{const_cast<uint8_t*>(proofs), w.S.p, w.P.p, w.status.p, l, w.Bpad};
@@ -2488,7 +2490,7 @@ struct Table : mp_table {
       SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
       MP_RUN(k_sigma_verdict, C, B, 1, va);
     }
-    UnmaskSumArgs ua{w.P.p, w.status.p, signer, op.c1.p, op.cstat.p, op.sumJ.p, token_status, card_status, w.Bpad, (uint32_t)K, T, l.a};
+    UnmaskSumArgs ua{w.P.p, w.status.p, signer, op.c1.p, op.cstat.p, op.sumJ.p, token_status, card_status, w.Bpad, (uint32_t)K, T, l.a, first};
     MP_RUN(k_unmask_sum, C, Cn, 1, ua);
     normalize_flat(op.sumJ.p, op.sumP.p, op.scratch.p, Cn);
     CardMatchArgs ma{op.sumP.p, card_status, plain, out_plain, out_index, (uint32_t)n_plain};
@@ -2497,9 +2499,9 @@ struct Table : mp_table {
   }
   int unmask_host(size_t K, const uint8_t* keys, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer, const uint8_t* tokens,
                   const uint8_t* proofs, size_t n_plain, const uint8_t* plain, uint8_t* out_plain, uint32_t* out_index,
-                  int32_t* token_status, int32_t* card_status) override {
+                  int32_t* token_status, int32_t* card_status, const uint32_t* first, size_t lanes) override {
     rt::Stream s = ctx->stream;
-    const size_t B = C_ * T, psz = 2 * (size_t)G_::PB + 32;
+    const size_t B = first ? lanes : C_ * T, psz = 2 * (size_t)G_::PB + 32;
     const int rc = check_card_list(n_plain, plain);
     if (rc != MP_OK) return rc;
     DevBuf<uint8_t> dk, dc, dt, dp, dl, dout;
@@ -2514,7 +2516,7 @@ struct Table : mp_table {
     rt::h2d(dp.p, proofs, B * psz, s);
     rt::h2d(dsg.p, signer, B * 4, s);
     if (n_plain) rt::h2d(dl.p, plain, n_plain * G_::PB, s);
-    unmask_dev(K, dk.p, C_, dc.p, T, dsg.p, dt.p, dp.p, n_plain, dl.p, dout.p, didx.p, dts.p, dcs.p, true);
+    unmask_dev(K, dk.p, C_, dc.p, T, dsg.p, dt.p, dp.p, n_plain, dl.p, dout.p, didx.p, dts.p, dcs.p, true, first, lanes);
     rt::d2h(out_plain, dout.p, C_ * G_::PB, s);
     rt::d2h(out_index, didx.p, C_ * 4, s);
     rt::d2h(token_status, dts.p, B * 4, s);
@@ -2524,9 +2526,9 @@ struct Table : mp_table {
   }
   // token = sk[signer] c0 first: the hedged nonce hashes the whole statement, the token included (k_sigma_init)
   void reveal_host(size_t K, const uint8_t* keys, const uint8_t* sks, size_t C_, const uint8_t* cards, uint32_t T, const uint32_t* signer,
-                   const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status) override {
+                   const uint8_t* seeds, uint8_t* out_tokens, uint8_t* out_proofs, int32_t* status, const uint32_t* first, size_t lanes) override {
     rt::Stream s = ctx->stream;
-    const uint32_t B = (uint32_t)(C_ * T);
+    const uint32_t B = (uint32_t)(first ? lanes : C_ * T);
     const size_t psz = 2 * (size_t)G_::PB + 32;
     open_prepare(B);
     Workspace& w = op.w;
@@ -2540,7 +2542,7 @@ struct Table : mp_table {
     rt::h2d(dc.p, cards, C_ * 2 * G_::PB, s);
     rt::h2d(dseed.p, seeds, (size_t)B * 32, s);
     rt::h2d(dsg.p, signer, (size_t)B * 4, s);
-    OpenStmtArgs sa = open_stmt_args(K, dk.p, dc.p, T, dsg.p);
+    OpenStmtArgs sa = open_stmt_args(K, dk.p, dc.p, T, dsg.p, first, C_);
     sa.sks = dx.p;
     MP_RUN(k_open_stmt, C, B, 4, sa);
     check_subgroup(w, B, l.g, 1);          // c0 and the key, as the sigma calls test bases and publics (the token is computed here)
@@ -2785,11 +2787,11 @@ struct Table : mp_table {
     rt::d2h(status, dst.p, C_ * 4, s);
     rt::stream_sync(s);
   }
-  // seating: lane = table * seats + seat
+  // seating: lane = table * seats + seat, or with an offsets array the lanes first[table] .. first[table + 1] - 1
   void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init, uint8_t* out_keys,
-                           int32_t* player_status, int32_t* table_status) override {
+                           int32_t* player_status, int32_t* table_status, const uint32_t* first, size_t lanes) override {
     rt::Stream s = ctx->stream;
-    const uint32_t Tn = (uint32_t)tables, B = Tn * seats;
+    const uint32_t Tn = (uint32_t)tables, B = first ? (uint32_t)lanes : Tn * seats;
     const size_t psz = (size_t)G_::PB + 32;
     deal_prepare(B);
     Workspace& w = deal.w;
@@ -2815,7 +2817,7 @@ struct Table : mp_table {
       SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 5};
       MP_RUN(k_sigma_verdict, C, B, 1, va);
     }
-    KeySumArgs ka{w.P.p, w.status.p, deal.sumJ.p, dps.p, dts.p, w.Bpad, seats, l.a};
+    KeySumArgs ka{w.P.p, w.status.p, deal.sumJ.p, dps.p, dts.p, w.Bpad, seats, l.a, first};
     MP_RUN(k_key_sum, C, Tn, 1, ka);
     normalize_flat(deal.sumJ.p, deal.sumP.p, deal.scratch.p, Tn);
     StorePointsArgs so{dout.p, deal.sumP.p, Tn, 1, 0};      // (the identity is zero bytes on the wire: a refused table's key)

@@ -167,6 +167,7 @@ struct KeySumArgs {
   int32_t* player_status;   // [lanes] out
   int32_t* table_status;    // [tables] out
   uint32_t Bpad, seats, a_slot;
+  const uint32_t* first;    // [tables + 1] offsets (then seats is not read), or nullptr: the table's lanes are k * seats .. k * seats + seats - 1
 };
 // One lane per table (the shape of k_unmask_sum).  The table's word is the first of its seats' that is not 0, in seat order: the
 // reference stops at the first bad proof.  A table whose proofs all verified gets the sum of its keys as they are given; every
@@ -174,9 +175,9 @@ struct KeySumArgs {
 // rare branches.
 template <class C>
 MP_HD void body_key_sum(const KeySumArgs& a, uint32_t k, uint32_t y) {
+  const uint32_t b0 = a.first ? a.first[k] : k * a.seats, b1 = a.first ? a.first[k + 1] : b0 + a.seats;
   int32_t first = 0;
-  for (uint32_t j = 0; j < a.seats; ++j) {
-    const uint32_t b = k * a.seats + j;
+  for (uint32_t b = b0; b < b1; ++b) {
     const int32_t st = a.status[b];
     a.player_status[b] = st;
     if (first == 0) first = st;
@@ -184,7 +185,7 @@ MP_HD void body_key_sum(const KeySumArgs& a, uint32_t k, uint32_t y) {
   Jac<C> acc = jac_inf<C>();
   if (first == 0) {
 #pragma unroll 1
-    for (uint32_t j = 0; j < a.seats; ++j) jac_madd_ip<C>(acc, ld_aff<C>(a.P + p_off<C>(a.a_slot, a.Bpad, k * a.seats + j)));
+    for (uint32_t b = b0; b < b1; ++b) jac_madd_ip<C>(acc, ld_aff<C>(a.P + p_off<C>(a.a_slot, a.Bpad, b)));
   }
   st_jac<C>(a.sumJ + (size_t)k * Geo<C>::JW, acc);
   a.table_status[k] = first;

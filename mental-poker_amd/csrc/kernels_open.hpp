@@ -2,7 +2,8 @@
 // player, and whoever opens it verifies the proofs and computes c1 - sum of the tokens
 // [REF barnett-smart-card-protocol/src/discrete_log_cards/mod.rs:300-378, examples/round.rs:159-206, 352-430].
 // The statements of the T tokens of C cards are assembled on the device from the compact inputs (keys, cards, signer indices,
-// tokens), lane b = c * T + j; transcript, check MSMs and verdict are those of kernels_sigma.hpp with
+// tokens), lane b = c * T + j -- or, with an offsets array `first` ([C + 1], device memory), the lanes first[c] .. first[c+1] - 1 for
+// card c, so that the cards of one call may carry different numbers of tokens; transcript, check MSMs and verdict are those of kernels_sigma.hpp with
 //   bases (c0, G), publics (token, pk[signer]), fs_init = Blake2s("Reveal Proof").
 // The token sums and the card lookup have one lane per card.
 #pragma once
@@ -29,14 +30,27 @@ struct OpenStmtArgs {
   uint32_t fs_seed[8];
   SigmaLay l;
   uint32_t Bpad, K, T, g_base;
+  const uint32_t* first;    // [C + 1] offsets (then T is not read), or nullptr: lane b = c * T + j
+  uint32_t C;               // the number of cards, read with `first` only
 };
+// The card of lane b under an offsets array: the last c with first[c] <= b.  A binary search, at most 21 probes (C <= 2^20) of an
+// array that every lane of the launch reads and that stays in cache.  The host has checked first[0] = 0 < first[1] < ... < first[C]
+// = the number of lanes, so the answer is below C for every lane of the launch.
+MP_HD uint32_t card_of_lane(const uint32_t* first, uint32_t C, uint32_t b) {
+  uint32_t lo = 0, hi = C;          // first[lo] <= b < first[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 // x = lane, y = statement slot: 0 g_0 = c0 of the card, 1 g_1 = G, 2 a_0 = the token (revealing: the witness sk[signer] instead),
 // 3 a_1 = keys[signer].  A lane whose signer is past the key list gets MP_ERR_BAD_ARGUMENT from every y and the identity in every
 // slot, so that no later test can put another code in its place.
 template <class C>
 MP_HD void body_open_stmt(const OpenStmtArgs& a, uint32_t b, uint32_t y) {
   typedef typename C::FrP R;
-  const uint32_t c = b / a.T, sg = a.signer[b];
+  const uint32_t c = a.first ? card_of_lane(a.first, a.C, b) : b / a.T, sg = a.signer[b];
   const bool known = sg < a.K;
   if (!known) status_fail(a.status, b, ST_BAD_ARGUMENT);
   Aff<C> pt = aff_inf<C>();
@@ -44,7 +58,7 @@ MP_HD void body_open_stmt(const OpenStmtArgs& a, uint32_t b, uint32_t y) {
   if (y == 0) {
     const uint8_t* card = a.cards + (size_t)c * 2 * Geo<C>::PB;
     ok = wire_to_aff<C>(card, pt);
-    if (a.c1 && b == c * a.T) {      // the card's first lane brings c1 along
+    if (a.c1 && b == (a.first ? a.first[c] : c * a.T)) {      // the card's first lane brings c1 along
       Aff<C> q;
       if (!wire_to_aff<C>(card + Geo<C>::PB, q)) {
         a.cstat[c] = ST_BAD_ENCODING;
@@ -88,17 +102,18 @@ struct UnmaskSumArgs {
   int32_t* token_status;    // [B] out
   int32_t* card_status;     // [C] out
   uint32_t Bpad, K, T, a_slot;
+  const uint32_t* first;    // [C + 1] offsets (then T is not read), or nullptr: the card's lanes are c * T .. c * T + T - 1
 };
-// One lane per card.  Folds the lanes' status words into the card's (the first that is not 0, in j order: the reference stops at the
+// One lane per card.  Folds the lanes' status words into the card's (the first that is not 0, in lane order: the reference stops at the
 // first bad token) and, for a card whose tokens all verified, subtracts them from c1.  Every addition is the complete mixed addition
 // of curve.hpp: tokens at infinity, two equal tokens (a doubling), tokens that cancel, c1 = O and a sum that is c1 all take its
 // rare branches.
 template <class C>
 MP_HD void body_unmask_sum(const UnmaskSumArgs& a, uint32_t c, uint32_t y) {
   const int32_t cs = a.cstat[c];
+  const uint32_t b0 = a.first ? a.first[c] : c * a.T, b1 = a.first ? a.first[c + 1] : b0 + a.T;
   int32_t first = 0;
-  for (uint32_t j = 0; j < a.T; ++j) {
-    const uint32_t b = c * a.T + j;
+  for (uint32_t b = b0; b < b1; ++b) {
     int32_t st = a.status[b];
     if (a.signer[b] >= a.K)
       st = ST_BAD_ARGUMENT;
@@ -111,8 +126,7 @@ MP_HD void body_unmask_sum(const UnmaskSumArgs& a, uint32_t c, uint32_t y) {
   if (first == 0) {
     acc = jac_from_aff<C>(ld_aff<C>(a.c1 + (size_t)c * Geo<C>::PW));
 #pragma unroll 1
-    for (uint32_t j = 0; j < a.T; ++j)
-      jac_madd_ip<C>(acc, aff_neg<C>(ld_aff<C>(a.P + p_off<C>(a.a_slot, a.Bpad, c * a.T + j))));
+    for (uint32_t b = b0; b < b1; ++b) jac_madd_ip<C>(acc, aff_neg<C>(ld_aff<C>(a.P + p_off<C>(a.a_slot, a.Bpad, b))));
   }
   st_jac<C>(a.sumJ + (size_t)c * Geo<C>::JW, acc);
   a.card_status[c] = first;

@@ -393,27 +393,35 @@ class DLCards:
 
     # -- opening cards in batches: compute_reveal_token / unmask for many cards and players in one call each (mp_reveal_batch,
     #    mp_unmask_batch; statements, token sums and the card lookup run on the device)             [REF examples/round.rs:159-206, 352-430]
-    def _open_shape(self, n_keys, cards, signer):
+    def _open_shape(self, n_keys, cards, signer, counts=None):
+        """-> tokens per card, or with `counts` the list of them (cards of tables of different sizes: the ragged entry points)"""
         pb = self.engine.point_bytes
-        if not cards or len(signer) % len(cards) or not signer or not n_keys:
+        if counts is not None:
+            counts = [int(n) for n in counts]
+            if not cards or not n_keys or len(counts) != len(cards) or any(n < 1 for n in counts) or sum(counts) != len(signer):
+                raise CardProtocolError.io("counts must name the number of tokens (at least one) of every card, len(signer) in all")
+        elif not cards or len(signer) % len(cards) or not signer or not n_keys:
             raise CardProtocolError.io("signer must name the same number of players (at least one) for every card")
         if any(len(bytes(c)) != 2 * pb for c in cards):
             raise CardProtocolError.io("a card is %d bytes" % (2 * pb))
-        return len(signer) // len(cards)
+        return counts if counts is not None else len(signer) // len(cards)
 
-    def compute_reveal_tokens(self, rng_seeds, pp, players, cards, signer):
+    def compute_reveal_tokens(self, rng_seeds, pp, players, cards, signer, counts=None):
         """players: [(pk, sk)]; cards: masked cards; signer[c * T + j]: index into players of whoever gives token j of card c;
-        rng_seeds: one fresh 32-byte seed per (card, token) -> [(RevealToken, ZKProofReveal)] in the order of signer"""
-        T = self._open_shape(len(players), cards, signer)
+        rng_seeds: one fresh 32-byte seed per (card, token) -> [(RevealToken, ZKProofReveal)] in the order of signer.
+        counts: tokens per card where the cards differ (sum(counts) == len(signer)): the signers of card c then follow those of card
+        c - 1 (mp_reveal_ragged_batch)"""
+        T = self._open_shape(len(players), cards, signer, counts)
         pb = self.engine.point_bytes
         if len(rng_seeds) != len(signer) or any(len(bytes(s)) != 32 for s in rng_seeds):
             raise CardProtocolError.io("one 32-byte prover seed per token")
         if any(len(bytes(pk)) != pb for pk, _ in players) or any(not 0 <= int(g) < len(players) for g in signer):
             raise CardProtocolError.io("a key is %d bytes, a signer an index into the players" % pb)
         try:
-            tok, prf, st = self._t(pp).reveal_batch(b"".join(bytes(pk) for pk, _ in players), _scalar_bytes([sk for _, sk in players]),
-                                                    b"".join(bytes(c) for c in cards), T, [int(g) for g in signer],
-                                                    b"".join(bytes(s) for s in rng_seeds))
+            t = self._t(pp)
+            tok, prf, st = (t.reveal_batch if counts is None else t.reveal_ragged_batch)(
+                b"".join(bytes(pk) for pk, _ in players), _scalar_bytes([sk for _, sk in players]), b"".join(bytes(c) for c in cards), T,
+                [int(g) for g in signer], b"".join(bytes(s) for s in rng_seeds))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         bad = [v for v in st if v != 0]
@@ -422,11 +430,12 @@ class DLCards:
         psz = 2 * pb + 32
         return [(tok[l * pb:(l + 1) * pb], prf[l * psz:(l + 1) * psz]) for l in range(len(signer))]
 
-    def open_cards(self, pp, keys, cards, signer, tokens, proofs, card_list):
+    def open_cards(self, pp, keys, cards, signer, tokens, proofs, card_list, counts=None):
         """keys: the players' public keys; signer / tokens / proofs: per (card, token) as compute_reveal_tokens orders them; card_list:
         the plaintext cards to look the results up in.  -> per card (plaintext, index in card_list | None), or the error `unmask`
-        raises for it: CardProtocolError("ProofVerificationError", CryptoError("Chaum-Pedersen")) / CardProtocolError.io(...)"""
-        T = self._open_shape(len(keys), cards, signer)
+        raises for it: CardProtocolError("ProofVerificationError", CryptoError("Chaum-Pedersen")) / CardProtocolError.io(...).
+        counts: tokens per card where the cards differ, as compute_reveal_tokens takes it (mp_unmask_ragged_batch)"""
+        T = self._open_shape(len(keys), cards, signer, counts)
         pb = self.engine.point_bytes
         psz = 2 * pb + 32
         if len(tokens) != len(signer) or len(proofs) != len(signer) or any(len(bytes(t)) != pb for t in tokens) or \
@@ -435,9 +444,10 @@ class DLCards:
         if any(not 0 <= int(g) < 1 << 32 for g in signer):
             raise CardProtocolError.io("a signer is an index into the keys")
         try:
-            plain, idx, _, cs = self._t(pp).unmask_batch(b"".join(bytes(k) for k in keys), b"".join(bytes(c) for c in cards), T,
-                                                         [int(g) for g in signer], b"".join(bytes(t) for t in tokens),
-                                                         b"".join(bytes(p) for p in proofs), b"".join(bytes(p) for p in card_list))
+            t = self._t(pp)
+            plain, idx, _, cs = (t.unmask_batch if counts is None else t.unmask_ragged_batch)(
+                b"".join(bytes(k) for k in keys), b"".join(bytes(c) for c in cards), T, [int(g) for g in signer],
+                b"".join(bytes(t) for t in tokens), b"".join(bytes(p) for p in proofs), b"".join(bytes(p) for p in card_list))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         out = []
@@ -510,19 +520,23 @@ class DLCards:
         return self._verify_deal(_native.Table.DEAL_REMASK, pp, shared_keys, key_index, original_cards, remasked_cards, proofs)
 
     def compute_aggregate_keys(self, pp, tables):
-        """`compute_aggregate_key` for many tables: tables = [[(pk, proof, player_public_info)]], the same number of players at each
+        """`compute_aggregate_key` for many tables: tables = [[(pk, proof, player_public_info)]], at least one player at each (tables
+        of one size go through mp_aggregate_keys_batch, tables of different sizes through mp_aggregate_keys_ragged_batch)
         -> per table the AggregatePublicKey, or the error `compute_aggregate_key` raises for it:
         CardProtocolError("ProofVerificationError", CryptoError("Schnorr Identification")) / CardProtocolError.io(...)"""
         pb = self.engine.point_bytes
-        if not tables or not tables[0] or any(len(t) != len(tables[0]) for t in tables):
-            raise CardProtocolError.io("at least one table, and the same number of players (at least one) at each")
+        if not tables or any(not t for t in tables):
+            raise CardProtocolError.io("at least one table, and at least one player at each")
         rows = [row for t in tables for row in t]
         if any(len(bytes(pk)) != pb or len(bytes(proof)) != pb + 32 for pk, proof, _ in rows):
             raise CardProtocolError.io("a key is %d bytes, a proof of key ownership %d" % (pb, pb + 32))
         try:
-            keys, _, ts = self._t(pp).aggregate_keys_batch(len(tables), len(tables[0]), b"".join(bytes(pk) for pk, _, _ in rows),
-                                                           b"".join(bytes(proof) for _, proof, _ in rows),
-                                                           b"".join(self.engine.blake2s(KEY_OWN_RNG_SEED + bytes(info)) for _, _, info in rows))
+            lanes = (b"".join(bytes(pk) for pk, _, _ in rows), b"".join(bytes(proof) for _, proof, _ in rows),
+                     b"".join(self.engine.blake2s(KEY_OWN_RNG_SEED + bytes(info)) for _, _, info in rows))
+            if all(len(t) == len(tables[0]) for t in tables):
+                keys, _, ts = self._t(pp).aggregate_keys_batch(len(tables), len(tables[0]), *lanes)
+            else:
+                keys, _, ts = self._t(pp).aggregate_keys_ragged_batch([len(t) for t in tables], *lanes)
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         return [keys[k * pb:(k + 1) * pb] if v == 0 else CardProtocolError("ProofVerificationError", CryptoError(self.engine.check_name(v))) if v > 0
@@ -585,6 +599,38 @@ class DLCards:
             raise CardProtocolError.io(str(e))
         return [None if s == 0 else (CryptoError(self.engine.check_name(s)) if s > 0 else CardProtocolError.io(self.engine.check_name(s)))
                 for s in st]
+
+    def verify_shuffle_chains(self, pp, chains):
+        """the shuffle chains of many tables, of different lengths, in one call (mp_verify_shuffle_chain_ragged).  chains: per table
+        (key_or_keys, decks, proofs) -- the table's aggregate key, or one key per link; links + 1 decks, deck j + 1 the output of link j;
+        one proof per link, at least one -> per table a list with, per link, None or the error verify_shuffle raises for it"""
+        pb, N = self.engine.point_bytes, pp.m * pp.n
+        psz = self.engine.proof_size(pp.m, pp.n)
+        if not chains:
+            raise CardProtocolError.io("at least one table")
+        links, keys, decks, proofs = [], [], [], []
+        for key, dks, prfs in chains:
+            ks = [bytes(key)] * len(prfs) if isinstance(key, (bytes, bytearray)) else [bytes(k) for k in key]
+            if not prfs or len(dks) != len(prfs) + 1 or len(ks) != len(prfs):
+                raise CardProtocolError.io("a chain is at least one link: links + 1 decks, one proof per link, one key or one key per link")
+            if any(len(k) != pb for k in ks) or any(len(bytes(p)) != psz for p in prfs) or \
+                    any(len(d) != N or any(len(bytes(c)) != 2 * pb for c in d) for d in dks):
+                raise CardProtocolError.io("a key is %d bytes, a proof %d, a deck m*n cards of %d" % (pb, psz, 2 * pb))
+            links.append(len(prfs))
+            keys += ks
+            decks += [b"".join(bytes(c) for c in d) for d in dks]
+            proofs += [bytes(p) for p in prfs]
+        try:
+            st = self.table(pp, keys[0]).verify_shuffle_chain_ragged(links, b"".join(decks), b"".join(proofs), b"".join(keys))
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+        words = [None if s == 0 else (CryptoError(self.engine.check_name(s)) if s > 0 else CardProtocolError.io(self.engine.check_name(s)))
+                 for s in st]
+        out, o = [], 0
+        for n in links:
+            out.append(words[o:o + n])
+            o += n
+        return out
 
     # -- secrets drawn on the device from seeds ("mpshuffle secret stream v1", include/mpshuffle.h; secret_stream below is the CPU
     #    statement): one fresh 32-byte CSPRNG seed per proof / per player, never reused; the seed is all a caller has to store
