@@ -2,7 +2,8 @@
 """Tables of different sizes in one call each: five tables with 2, 3, 5, 9 and 3 seats and a small deck of eight cards (m=2, n=4).  One
 compute_aggregate_keys call seats all 22 players (mp_aggregate_keys_ragged_batch: the tables differ in size); every table deals its deck
 and every player shuffles it once, so a table's chain has as many links as it has seats; one verify_shuffle_chains call verifies all 22
-links (mp_verify_shuffle_chain_ragged); at the showdown every table opens its first three cards, one token per seated player and card, in
+links (mp_verify_shuffle_chain_ragged), and one mp_verify_shuffle_chain_ragged_dev call verifies them once more from device buffers, where a
+prover leaves them; at the showdown every table opens its first three cards, one token per seated player and card, in
 one compute_reveal_tokens and one open_cards call (mp_reveal_ragged_batch, mp_unmask_ragged_batch: 2 to 9 tokens per card)
 [REF barnett-smart-card-protocol/examples/round.rs, one table of four there]."""
 import importlib
@@ -20,6 +21,7 @@ SHOWN = 3
 
 
 def main():
+    import torch      # (before the library is loaded: torch ships a HIP runtime of its own)
     m, n = 2, 4
     num_cards = m * n
     cards = mp.DLCards("stark", device=0)
@@ -75,6 +77,20 @@ def main():
     bad = cards.verify_shuffle_chains(pp, swapped)
     assert isinstance(bad[1][1], mp.CryptoError) and [v for row in bad for v in row].count(None) == sum(SEATS) - 1
 
+    # once more from device buffers in the same table-major layout: the links are a host list, the words are final after sync()
+    gpu = torch.device("cuda:0")
+    dev = lambda raw: torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(gpu)      # noqa: E731
+    d_keys = dev(b"".join(joint[k] * seats for k, seats in enumerate(SEATS)))
+    d_decks = dev(b"".join(card for _, decks, _ in chains for deck in decks for card in deck))
+    d_proofs = dev(b"".join(proof for _, _, proofs in chains for proof in proofs))
+    d_status = torch.full((sum(SEATS),), -1, dtype=torch.int32, device=gpu)
+    torch.cuda.synchronize()
+    table = cards.table(pp, joint[0])
+    table.verify_shuffle_chain_ragged_dev(SEATS, d_keys.data_ptr(), d_decks.data_ptr(), d_proofs.data_ptr(), d_status.data_ptr())
+    cards.engine.sync()
+    assert d_status.cpu().tolist() == [0] * sum(SEATS), d_status.cpu().tolist()
+    passes, pieces = table.chain_ragged_stats()[:2]
+
     # showdown: the first three cards of every table, one token from every player at the table
     shown, signer, counts, at = [], [], [], 0
     for k, seats in enumerate(SEATS):
@@ -99,6 +115,7 @@ def main():
 
     print("%d players seated at %d tables of %s seats in %.1f ms" % (len(players), len(SEATS), SEATS, (t1 - t0) * 1e3))
     print("%d shuffle links in %d chains verified in %.1f ms" % (sum(SEATS), len(SEATS), (t3 - t2) * 1e3))
+    print("the same links verified from device buffers in %d passes of %d pieces" % (passes, pieces))
     print("%d reveal tokens made and %d cards opened in %.1f ms" % (len(signer), len(shown), (t5 - t4) * 1e3))
     for k, seats in enumerate(SEATS):
         print("table %d (%d seats) shows %s" % (k, seats, " ".join(NAMES[idx] for _, idx in opened[k * SHOWN:(k + 1) * SHOWN])))

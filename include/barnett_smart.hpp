@@ -470,6 +470,19 @@ class DLCardsT {
     }
     return out;
   }
+  // The same over device arrays in the table-major layout of mp_verify_shuffle_chain_ragged_dev (16-byte aligned; d_keys: one key per
+  // link; any_key: a key of pp, to bind the table); links is a host vector.  Enqueued: d_status is final after sync().
+  void verify_shuffle_chains_dev(const Parameters& pp, const PublicKey& any_key, const std::vector<uint32_t>& links, const void* d_keys,
+                                 const void* d_decks, const void* d_proofs, void* d_status) {
+    if (links.empty()) throw CardProtocolError("verify_shuffle_chains_dev: at least one table");
+    bind_any(pp, any_key);
+    if (mp_verify_shuffle_chain_ragged_dev(table_, links.size(), links.data(), d_keys, d_decks, d_proofs, d_status) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+  }
+  // how verify_shuffle_chains[_dev] cut their chains on the table bound now: MP_CHAIN_PIECES_WHOLE or MP_CHAIN_PIECES_BINARY (cut only where that saves passes); same words
+  void set_chain_pieces(int mode) {
+    if (!table_ || mp_set_chain_pieces(table_, mode) != MP_OK) throw CardProtocolError(table_ ? mp_last_error() : "set_chain_pieces: no table bound yet");
+  }
 
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
   mp_pool_table* pool_table() const { return ptable_; }      // NULL without a device list

@@ -218,16 +218,53 @@ int mp_verify_shuffle_chain(mp_table* t, size_t tables, uint32_t links, const ui
                             const uint8_t* proofs, int32_t* status);
 int mp_verify_shuffle_chain_dev(mp_table* t, size_t tables, uint32_t links, const void* d_keys, const void* d_decks, const void* d_proofs,
                                 void* d_status);
-/* mp_verify_shuffle_chain_ragged: the tables of one call may have chains of different lengths, links[t] >= 1 links for table t (host
- * buffers only).  The layout is table-major -- link-major needs equal lengths: with off(t) = links[0] + ... + links[t-1], table t owns
+/* mp_verify_shuffle_chain_ragged[_dev]: the tables of one call may have chains of different lengths, links[t] >= 1 links for table t.
+ * The layout is table-major -- link-major needs equal lengths: with off(t) = links[0] + ... + links[t-1], table t owns
  * the decks off(t) + t .. off(t) + t + links[t] (consecutive: deck j + 1 is the output of link j) and the proofs, status words and keys
- * off(t) .. off(t) + links[t] - 1 (keys: one per link; NULL = the mp_table's own key).  The tables are grouped by links[t]; each group is
- * gathered on the host into the link-major arrays above and verified by one mp_verify_shuffle_chain call; once every group has been
- * verified the status words are scattered back (on a return other than MP_OK the status array is as it was):
- * mp_set_chain_group, _max_links and _slice apply to each group as to a call of that group alone, and the status words are those of
- * mp_verify_shuffle_batch[_keys] link by link.  tables == 0, a links[t] of 0 or above 4 095, or 2^31 proofs and more: MP_ERR_BAD_ARGUMENT. */
+ * off(t) .. off(t) + links[t] - 1 (keys: one per link; NULL = the mp_table's own key).
+ *
+ * Pieces and passes.  The chain of table t is cut into PIECES (t, first link a, length l) -- the links a .. a + l - 1 and their l + 1
+ * decks --, and the pieces of one length l, in (t, a) order, are a PASS: gathered ON THE DEVICE into link-major staging (one launch per
+ * pass, kernels_chain_pieces.hpp) and verified by one mp_verify_shuffle_chain_dev call of (pieces of the pass) tables x l links.
+ * mp_set_chain_group, _max_links and _slice apply to each pass as to a call of that pass alone.  Once every pass has been enqueued, ONE
+ * launch scatters the words of all passes into the status array: on a return other than MP_OK the status array is as it was.  The
+ * status words are those of mp_verify_shuffle_batch[_keys] link by link, whatever the decomposition (mp_set_chain_pieces):
+ *   MP_CHAIN_PIECES_WHOLE   one piece per table; the passes are the distinct values of links[t], ascending.  Every inner deck of a chain
+ *                           is a base of its equation once.
+ *   MP_CHAIN_PIECES_BINARY  the chain is cut front to back into pieces whose lengths are the powers of two in links[t], largest first
+ *                           (7 = 4 + 2 + 1); the passes are the distinct piece lengths, ascending: at most 12 whatever the lengths, 4 for
+ *                           2 to 10 links, each of them wide.  A deck at a cut is a base of two equations.  The cut is made only
+ *                           where it saves passes: a call in which whole chains need no more passes than their pieces -- every call
+ *                           whose chains have one length -- is verified as under MP_CHAIN_PIECES_WHOLE.
+ * tables == 0, a links[t] of 0 or above 4 095, 2^31 proofs and more, a keyless table without keys: MP_ERR_BAD_ARGUMENT, nothing is
+ * enqueued and no buffer is touched.
+ *
+ * _dev: d_keys (or NULL), d_decks, d_proofs and d_status are device arrays in the layout above, 16-byte aligned; `links` is ALWAYS a host
+ * array, with the rules of `first` of the other ragged _dev calls: it is copied and the copy is validated before anything is enqueued,
+ * only the copy is used, and the caller's array is consumed when the call returns.  d_status is final after mp_sync.
+ * The host-buffer form uploads the caller's arrays as they are, once, takes the _dev path and downloads the words, once: the library
+ * copies no deck, proof or key within host memory.
+ *
+ * Staging.  The table keeps the staging of a pass, the words of all passes and the descriptors; they grow only, a call that fits what is
+ * there allocates nothing, and they go with mp_table_destroy.  With P passes of G_p pieces of l_p links, deck_bytes = 2 m n point_bytes:
+ *   max_p (l_p + 1) G_p * deck_bytes  +  max_p l_p G_p * (proof_bytes + point_bytes if keys are passed)
+ *   + 4 * sum(links)  +  16 * pieces  +  24 * P      bytes
+ * (the host-buffer form keeps device copies of its three arrays and of the status words on top). */
+#define MP_CHAIN_PIECES_WHOLE 0
+#define MP_CHAIN_PIECES_BINARY 1
 int mp_verify_shuffle_chain_ragged(mp_table* t, size_t tables, const uint32_t* links, const uint8_t* shared_keys, const uint8_t* decks,
                                    const uint8_t* proofs, int32_t* status);
+int mp_verify_shuffle_chain_ragged_dev(mp_table* t, size_t tables, const uint32_t* links, const void* d_keys, const void* d_decks,
+                                       const void* d_proofs, void* d_status);
+/* How mp_verify_shuffle_chain_ragged[_dev] cuts its chains: MP_CHAIN_PIECES_WHOLE or MP_CHAIN_PIECES_BINARY (anything else:
+ * MP_ERR_BAD_ARGUMENT).  Status words do not depend on it. */
+int mp_set_chain_pieces(mp_table* t, int mode);
+/* The last mp_verify_shuffle_chain_ragged[_dev] call on this table that passed its argument checks: out[0] passes, [1] pieces, [2] tables,
+ * [3] links, [4] bytes moved by the gather launches, [5] bytes of decks, proofs and keys the library copied within host memory -- the constant
+ * 0, not a counter: the call has no such copy, and the word keeps its place for callers that budgeted the host staging of the earlier
+ * implementation --, [6] pieces of the widest pass, [7] the cut that was made (MP_CHAIN_PIECES_WHOLE also where the table is set to
+ * MP_CHAIN_PIECES_BINARY and the cut would have saved no pass).  Takes the context's lock. */
+int mp_chain_ragged_stats(const mp_table* t, uint64_t out[8]);
 int mp_sync(mp_ctx* ctx);
 int mp_reserve(mp_table* t, size_t B);           /* pre-allocate the batch workspace for B proofs */
 /* Every table holds six static work splits with identical results: a throughput plan (large sub-jobs, fewest operations) and five

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(HERE)
 
 CURVE_IDS = {"stark": 0, "bn254": 1, "secp256k1": 2, "bls12_377": 3}
 MP_ERR_BAD_ENCODING, MP_ERR_BAD_PERMUTATION, MP_ERR_BAD_ARGUMENT, MP_ERR_NO_DEVICE, MP_ERR_INTERNAL = -1, -2, -3, -4, -5
+CHAIN_PIECES_WHOLE, CHAIN_PIECES_BINARY = 0, 1
 
 SYMBOLS = [
     "mp_ctx_create", "mp_ctx_destroy", "mp_last_error", "mp_check_name", "mp_proof_size", "mp_params_size",
@@ -29,7 +30,7 @@ SYMBOLS = [
     "mp_mask_batch", "mp_verify_mask_batch", "mp_verify_mask_batch_dev", "mp_aggregate_keys_batch",
     "mp_set_sigma_screen", "mp_sigma_screen_stats",
     "mp_reveal_ragged_batch", "mp_unmask_ragged_batch", "mp_unmask_ragged_batch_dev", "mp_aggregate_keys_ragged_batch",
-    "mp_verify_shuffle_chain_ragged",
+    "mp_verify_shuffle_chain_ragged", "mp_verify_shuffle_chain_ragged_dev", "mp_set_chain_pieces", "mp_chain_ragged_stats",
     "mp_sample_secrets_batch", "mp_sample_secrets_batch_dev", "mp_shuffle_and_remask_batch_seeded", "mp_shuffle_and_remask_batch_seeded_dev",
     "mp_keygen_batch",
     "mp_pool_create", "mp_pool_destroy", "mp_pool_size", "mp_pool_member_ctx", "mp_pool_table_create", "mp_pool_table_destroy",
@@ -254,6 +255,9 @@ def bind(cdll):
     cdll.mp_verify_shuffle_chain.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, i32p]
     cdll.mp_verify_shuffle_chain_dev.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32] + [c.c_void_p] * 4
     cdll.mp_verify_shuffle_chain_ragged.argtypes = [c.c_void_p, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_verify_shuffle_chain_ragged_dev.argtypes = [c.c_void_p, c.c_size_t, u32p] + [c.c_void_p] * 4
+    cdll.mp_set_chain_pieces.argtypes = [c.c_void_p, c.c_int]
+    cdll.mp_chain_ragged_stats.argtypes = [c.c_void_p, c.POINTER(c.c_uint64)]
     cdll.mp_sync.argtypes = [c.c_void_p]
     cdll.mp_reserve.argtypes = [c.c_void_p, c.c_size_t]
     cdll.mp_set_latency_batch.argtypes = [c.c_void_p, c.c_size_t]
@@ -692,6 +696,12 @@ class Table:
                                                               _in(proofs), st))
         return list(st)[:total]
 
+    def verify_shuffle_chain_ragged_dev(self, links, d_keys, d_decks, d_proofs, d_status):
+        """verify_shuffle_chain_ragged over device arrays in the same table-major layout (16-byte aligned; d_keys None = the table's own
+        key); `links` is a host list.  d_status is final after Engine.sync()"""
+        lk = (ctypes.c_uint32 * max(len(links), 1))(*links)
+        self.eng._chk(self.lib.mp_verify_shuffle_chain_ragged_dev(self.h, len(links), lk, d_keys, d_decks, d_proofs, d_status))
+
     def verify_shuffle_chain_dev(self, tables, links, d_keys, d_decks, d_proofs, d_status):
         self.eng._chk(self.lib.mp_verify_shuffle_chain_dev(self.h, tables, links, d_keys, d_decks, d_proofs, d_status))
 
@@ -1086,6 +1096,19 @@ class Table:
     def set_chain_slice(self, tables_per_pass):
         """chain verification in passes of this many tables (0 = one pass if its workspace fits the free memory)"""
         self.eng._chk(self.lib.mp_set_chain_slice(self.h, tables_per_pass))
+
+    def set_chain_pieces(self, mode):
+        """how the ragged chain calls cut their chains: CHAIN_PIECES_WHOLE (one piece per table, a pass per distinct length) or
+        CHAIN_PIECES_BINARY (pieces of 2^k links, at most 12 passes; a call in which that would save no pass, such as chains of one
+        length, keeps its chains whole); same status words"""
+        self.eng._chk(self.lib.mp_set_chain_pieces(self.h, mode))
+
+    def chain_ragged_stats(self):
+        """the last ragged chain call: [passes, pieces, tables, links, bytes gathered on the device, bytes staged on the host (the constant 0: there is no
+        such copy), pieces of the widest pass, the cut that was made]"""
+        out = (ctypes.c_uint64 * 8)()
+        self.eng._chk(self.lib.mp_chain_ragged_stats(self.h, out))
+        return list(out)
 
     def chain_group_size(self, tables, links, keyed=False):
         """tables per chain equation a pass of `tables` tables x `links` links takes under the current settings"""

@@ -272,6 +272,13 @@ void mp_table_destroy(mp_table* t) {
       }
       rt::event_destroy(t->ragged_first_up);
     }
+    if (t->cp_plan_up) {
+      try {
+        rt::event_sync(t->cp_plan_up);
+      } catch (...) {
+      }
+      rt::event_destroy(t->cp_plan_up);
+    }
     for (auto& st : t->io) {
       if (st.up) rt::event_destroy(st.up);
       if (st.done) rt::event_destroy(st.done);
@@ -712,59 +719,170 @@ int mp_verify_shuffle_chain(mp_table* t, size_t tables, uint32_t links, const ui
   return MP_OK;
   MP_CATCH
 }
-// Chains of different lengths: the tables are grouped by their number of links, each group is gathered from the table-major arrays of the
-// caller into the link-major arrays of mp_verify_shuffle_chain, verified as a call of that group alone, and its words are scattered back.
+// ---- chains of different lengths: pieces and passes (include/mpshuffle.h; engine_base.hpp "Chains of different lengths")
+// The plan of one call.  The caller's links are copied into cp_links and checked THERE, before anything is enqueued; everything below is
+// derived from the copy.  Pieces: table by table, front to back -- one of links[t] links (WHOLE), or one per set bit of links[t] from the
+// highest down (BINARY, where that gives fewer passes).  Passes: the distinct piece lengths, ascending; walking the tables in order leaves the pieces of a pass in
+// (t, a) order.  cp_plan_host: [pieces][2] = deck row off(t) + t + a and proof row off(t) + a, the passes back to back; then
+// [passes][3] = first word, first piece, pieces.  Holds the context's lock.  -> MP_OK, or MP_ERR_BAD_ARGUMENT with nothing touched
+namespace {
+struct ChainPass {
+  uint32_t l;               // links of every piece of the pass
+  size_t G, piece, word;    // its pieces; its first piece and first status word among those of the call
+};
+}  // namespace
+static int chain_ragged_take(mp_table* t, size_t tables, const uint32_t* links, std::vector<ChainPass>& passes) {
+  static const char* const SHAPE = "mp_verify_shuffle_chain_ragged: 1 <= links[t] <= 4 095 for every table, less than 2^31 links in all";
+  if (tables >= ((size_t)1 << 31)) return fail(MP_ERR_BAD_ARGUMENT, SHAPE);
+  std::vector<uint32_t>& lk = t->cp_links;
+  lk.assign(links, links + tables);
+  uint64_t total = 0;
+  for (size_t k = 0; k < tables; ++k) {
+    if (lk[k] < 1 || lk[k] > 4095) return fail(MP_ERR_BAD_ARGUMENT, SHAPE);
+    total += lk[k];
+  }
+  if (total >= ((uint64_t)1 << 31)) return fail(MP_ERR_BAD_ARGUMENT, SHAPE);
+  // BINARY is there for fewer passes -- one per bit set in some links[t] against one per distinct length --, and a pass costs milliseconds
+  // whatever it holds (DESIGN.md "Ragged calls"): where whole chains need no more passes, as in every call whose chains have one length,
+  // they stay whole and no boundary deck is verified twice.  mp_chain_ragged_stats reports the cut that was made
+  std::vector<size_t> next(4096, 0);      // pieces of length l; then the slot of the next piece of that length
+  uint32_t bits_set = 0, lengths = 0;
+  for (size_t k = 0; k < tables; ++k) {
+    bits_set |= lk[k];
+    if (!next[lk[k]]) next[lk[k]] = ++lengths;
+  }
+  std::fill(next.begin(), next.end(), 0);
+  const bool binary = t->chain_pieces == MP_CHAIN_PIECES_BINARY && (uint32_t)__builtin_popcount(bits_set) < lengths;
+  for (size_t k = 0; k < tables; ++k) {
+    if (!binary) ++next[lk[k]];
+    for (uint32_t b = 2048; binary && b; b >>= 1)
+      if (lk[k] & b) ++next[b];
+  }
+  passes.clear();
+  size_t pieces = 0, words = 0, widest = 0;
+  for (uint32_t l = 1; l < 4096; ++l)
+    if (next[l]) {
+      const size_t G = next[l];
+      passes.push_back(ChainPass{l, G, pieces, words});
+      next[l] = pieces;
+      pieces += G;
+      words += (size_t)l * G;
+      widest = std::max(widest, G);
+    }
+  if (t->cp_plan_up)
+    rt::event_sync(t->cp_plan_up);      // (the upload of the previous call's descriptors has read the vector)
+  else
+    t->cp_plan_up = rt::event_create();
+  std::vector<uint64_t>& h = t->cp_plan_host;
+  h.assign(2 * pieces + 3 * passes.size(), 0);
+  uint64_t off = 0;
+  auto put = [&](size_t k, uint32_t a, uint32_t l) {
+    const size_t i = next[l]++;
+    h[2 * i] = off + k + a;
+    h[2 * i + 1] = off + a;
+  };
+  for (size_t k = 0; k < tables; ++k) {
+    if (!binary) put(k, 0, lk[k]);
+    uint32_t a = 0;
+    for (uint32_t b = 2048; binary && b; b >>= 1)
+      if (lk[k] & b) {
+        put(k, a, b);
+        a += b;
+      }
+    off += lk[k];
+  }
+  for (size_t p = 0; p < passes.size(); ++p) {
+    h[2 * pieces + 3 * p] = passes[p].word;
+    h[2 * pieces + 3 * p + 1] = passes[p].piece;
+    h[2 * pieces + 3 * p + 2] = passes[p].G;
+  }
+  const uint64_t st[8] = {passes.size(), pieces, tables, total, 0, 0, widest, (uint64_t)(binary ? MP_CHAIN_PIECES_BINARY : MP_CHAIN_PIECES_WHOLE)};
+  memcpy(t->cp_stats, st, sizeof st);
+  return MP_OK;
+}
+// the passes of a planned call over device arrays: one gather launch and one mp_verify_shuffle_chain_dev per pass on the context's
+// stream, the words of every pass kept in cp_words, and ONE scatter launch behind the last pass
+static int chain_ragged_passes(mp_table* t, const std::vector<ChainPass>& passes, const uint8_t* d_keys, const uint8_t* d_decks,
+                               const uint8_t* d_proofs, int32_t* d_status) {
+  rt::Stream s = t->ctx->stream;
+  const size_t pb = t->point_bytes, deck_bytes = (size_t)2 * t->N * pb, psz = proof_size_bytes(t->m, t->n, (uint32_t)pb);
+  const size_t pieces = (size_t)t->cp_stats[1], total = (size_t)t->cp_stats[3];
+  t->cp_plan.upload(t->cp_plan_host, s);
+  rt::event_record(t->cp_plan_up, s);
+  size_t max_d = 0, max_p = 0;
+  for (const ChainPass& p : passes) {
+    max_d = std::max(max_d, (size_t)(p.l + 1) * p.G);
+    max_p = std::max(max_p, (size_t)p.l * p.G);
+  }
+  t->cp_decks.alloc(max_d * deck_bytes, s, false);
+  t->cp_proofs.alloc(max_p * psz, s, false);
+  if (d_keys) t->cp_keys.alloc(max_p * pb, s, false);
+  t->cp_words.alloc(total, s, false);
+  for (const ChainPass& p : passes) {
+    t->cp_stats[4] += t->chain_piece_gather(t->cp_plan.p + 2 * p.piece, p.G, p.l, d_decks, d_proofs, d_keys, t->cp_decks.p, t->cp_proofs.p,
+                                            d_keys ? t->cp_keys.p : nullptr);
+    const int rc = mp_verify_shuffle_chain_dev(t, p.G, p.l, d_keys ? t->cp_keys.p : nullptr, t->cp_decks.p, t->cp_proofs.p, t->cp_words.p + p.word);
+    if (rc != MP_OK) return rc;
+  }
+  t->chain_piece_scatter(t->cp_plan.p, t->cp_plan.p + 2 * pieces, (uint32_t)passes.size(), t->cp_words.p, total, d_status);
+  return MP_OK;
+}
+int mp_verify_shuffle_chain_ragged_dev(mp_table* t, size_t tables, const uint32_t* links, const void* d_keys, const void* d_decks,
+                                       const void* d_proofs, void* d_status) {
+  if (!t || !tables || !links || !d_decks || !d_proofs || !d_status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged_dev: bad argument");
+  if (((uintptr_t)d_keys | (uintptr_t)d_decks | (uintptr_t)d_proofs) & 15u)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged_dev: the device arrays must be 16-byte aligned");
+  if (t->keyless && !d_keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: pass one key per link");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  std::vector<ChainPass> passes;
+  if (int bad = chain_ragged_take(t, tables, links, passes)) return bad;
+  NoPipeline nopipe(t);
+  return chain_ragged_passes(t, passes, (const uint8_t*)d_keys, (const uint8_t*)d_decks, (const uint8_t*)d_proofs, (int32_t*)d_status);
+  MP_CATCH
+}
+// host buffers: the caller's arrays go up as they are, the passes run as above, the words come down
 int mp_verify_shuffle_chain_ragged(mp_table* t, size_t tables, const uint32_t* links, const uint8_t* shared_keys, const uint8_t* decks,
                                    const uint8_t* proofs, int32_t* status) {
   if (!t || !tables || !links || !decks || !proofs || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: bad argument");
-  std::vector<size_t> off(tables + 1, 0);
-  for (size_t k = 0; k < tables; ++k) {
-    if (links[k] < 1 || links[k] > 4095) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: 1 <= links[t] <= 4 095 for every table");
-    off[k + 1] = off[k] + links[k];
-  }
-  if ((uint64_t)off[tables] >= ((uint64_t)1 << 31)) return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged: too many proofs for one call");
   if (t->keyless && !shared_keys) return fail(MP_ERR_BAD_ARGUMENT, "this table has no aggregate key: pass one key per link");
   MP_TRY
   MP_ENTER(t->ctx);
+  std::vector<ChainPass> passes;
+  if (int bad = chain_ragged_take(t, tables, links, passes)) return bad;
+  NoPipeline nopipe(t);
+  rt::Stream s = t->ctx->stream;
   const size_t pb = t->point_bytes, deck_bytes = (size_t)2 * t->N * pb, psz = proof_size_bytes(t->m, t->n, (uint32_t)pb);
-  std::vector<size_t> order(tables);
-  for (size_t k = 0; k < tables; ++k) order[k] = k;
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return links[a] < links[b]; });
-  // staging for one group at a time, sized once for the largest group and not zero-filled; the words of every group are kept until all
-  // groups have been verified, so that a call that fails half way leaves the caller's status array as it was
-  size_t max_d = 0, max_p = 0;
-  for (size_t i0 = 0; i0 < tables;) {
-    const uint32_t L = links[order[i0]];
-    size_t i1 = i0;
-    while (i1 < tables && links[order[i1]] == L) ++i1;
-    max_d = std::max(max_d, (size_t)(L + 1) * (i1 - i0));
-    max_p = std::max(max_p, (size_t)L * (i1 - i0));
-    i0 = i1;
+  const size_t total = (size_t)t->cp_stats[3];
+  t->cp_in_decks.alloc((total + tables) * deck_bytes, s, false);
+  t->cp_in_proofs.alloc(total * psz, s, false);
+  t->cp_in_status.alloc(total, s, false);
+  rt::h2d(t->cp_in_decks.p, decks, (total + tables) * deck_bytes, s);
+  rt::h2d(t->cp_in_proofs.p, proofs, total * psz, s);
+  if (shared_keys) {
+    t->cp_in_keys.alloc(total * pb, s, false);
+    rt::h2d(t->cp_in_keys.p, shared_keys, total * pb, s);
   }
-  std::unique_ptr<uint8_t[]> gd(new uint8_t[max_d * deck_bytes]), gp(new uint8_t[max_p * psz]), gk(new uint8_t[shared_keys ? max_p * pb : 1]);
-  std::vector<int32_t> gs(max_p), words(off[tables]);
-  for (size_t i0 = 0; i0 < tables;) {
-    const uint32_t L = links[order[i0]];
-    size_t i1 = i0;
-    while (i1 < tables && links[order[i1]] == L) ++i1;
-    const size_t G = i1 - i0;
-    for (size_t g = 0; g < G; ++g) {
-      const size_t k = order[i0 + g], o = off[k];
-      for (uint32_t j = 0; j <= L; ++j) memcpy(gd.get() + ((size_t)j * G + g) * deck_bytes, decks + (o + k + j) * deck_bytes, deck_bytes);
-      for (uint32_t j = 0; j < L; ++j) {
-        memcpy(gp.get() + ((size_t)j * G + g) * psz, proofs + (o + j) * psz, psz);
-        if (shared_keys) memcpy(gk.get() + ((size_t)j * G + g) * pb, shared_keys + (o + j) * pb, pb);
-      }
-    }
-    const int rc = mp_verify_shuffle_chain(t, G, L, shared_keys ? gk.get() : nullptr, gd.get(), gp.get(), gs.data());
-    if (rc != MP_OK) return rc;
-    for (size_t g = 0; g < G; ++g)
-      for (uint32_t j = 0; j < L; ++j) words[off[order[i0 + g]] + j] = gs[(size_t)j * G + g];
-    i0 = i1;
-  }
-  memcpy(status, words.data(), words.size() * sizeof(int32_t));
+  const int rc = chain_ragged_passes(t, passes, shared_keys ? t->cp_in_keys.p : nullptr, t->cp_in_decks.p, t->cp_in_proofs.p, t->cp_in_status.p);
+  if (rc != MP_OK) return rc;
+  rt::d2h(status, t->cp_in_status.p, total * 4, s);
+  rt::stream_sync(s);
   return MP_OK;
   MP_CATCH
+}
+int mp_set_chain_pieces(mp_table* t, int mode) {
+  if (!t) return fail(MP_ERR_BAD_ARGUMENT, "mp_set_chain_pieces: null table");
+  if (mode != MP_CHAIN_PIECES_WHOLE && mode != MP_CHAIN_PIECES_BINARY)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_set_chain_pieces: MP_CHAIN_PIECES_WHOLE or MP_CHAIN_PIECES_BINARY");
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
+  t->chain_pieces = mode;
+  return MP_OK;
+}
+int mp_chain_ragged_stats(const mp_table* t, uint64_t out[8]) {
+  if (!t || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_chain_ragged_stats: null argument");
+  std::lock_guard<std::recursive_mutex> mp_lock_(t->ctx->mu);
+  memcpy(out, t->cp_stats, sizeof t->cp_stats);
+  return MP_OK;
 }
 int mp_sync(mp_ctx* ctx) {
   if (!ctx) return fail(MP_ERR_BAD_ARGUMENT, "mp_sync: null");

@@ -273,6 +273,29 @@ struct mp_table {
   virtual void validate_decks_dev(size_t count, const uint8_t* decks, int32_t* status) = 0;
   virtual uint32_t chain_group_size(size_t T, uint32_t L, bool keyed) const = 0;
   size_t chain_last_slice = 0;    // tables per pass of the last mp_verify_shuffle_chain_dev call (mp_chain_plan)
+  // Chains of different lengths (capi.hip chain_ragged_take / chain_ragged_passes, kernels_chain_pieces.hpp).  The chain of table t is cut into PIECES (t, first
+  // link a, length l) -- one piece per table (MP_CHAIN_PIECES_WHOLE) or the binary expansion of links[t], largest first
+  // (MP_CHAIN_PIECES_BINARY) --, and the pieces of one length, in (t, a) order, are a PASS: gathered on the device into the link-major
+  // staging below and verified by one mp_verify_shuffle_chain_dev call.  chain_piece_gather -> bytes moved
+  int chain_pieces = MP_CHAIN_PIECES_BINARY;      // mp_set_chain_pieces
+  virtual size_t chain_piece_gather(const uint64_t* desc, size_t G, uint32_t l, const uint8_t* decks, const uint8_t* proofs, const uint8_t* keys,
+                                    uint8_t* sdecks, uint8_t* sproofs, uint8_t* skeys) = 0;
+  virtual void chain_piece_scatter(const uint64_t* desc, const uint64_t* pass, uint32_t passes, const int32_t* words, size_t total,
+                                   int32_t* status) = 0;
+  // the staging of a pass, sized for the largest pass of a call, and the words of all passes; they grow only and go with the table
+  mp::DevBuf<uint8_t> cp_decks, cp_proofs, cp_keys;
+  mp::DevBuf<int32_t> cp_words;
+  // the descriptors: [pieces][2] source rows, the passes back to back, then [passes][3] first word, first piece, pieces.  Built on the host
+  // from a validated copy of the caller's links (cp_links) and uploaded from cp_plan_host, which is not overwritten or freed before the
+  // event behind that upload has passed (as ragged_first_host below)
+  mp::DevBuf<uint64_t> cp_plan;
+  std::vector<uint64_t> cp_plan_host;
+  std::vector<uint32_t> cp_links;
+  mp::rt::Event cp_plan_up = nullptr;
+  // the device copies of the host-buffer call's arrays (mp_verify_shuffle_chain_ragged: one upload, one download)
+  mp::DevBuf<uint8_t> cp_in_decks, cp_in_proofs, cp_in_keys;
+  mp::DevBuf<int32_t> cp_in_status;
+  uint64_t cp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // mp_chain_ragged_stats
   virtual void remask_host(size_t count, const uint8_t* cards, const uint8_t* rho, uint8_t* out) = 0;
   virtual void msm_host(size_t n_msm, size_t k, const uint8_t* scalars, const uint8_t* points, uint8_t* out) = 0;
   virtual void commit_host(size_t count, size_t len, const uint8_t* values, const uint8_t* r, uint8_t* out) = 0;

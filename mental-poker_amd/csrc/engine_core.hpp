@@ -9,6 +9,7 @@
 #include "kernels_deal.hpp"
 #include "kernels_sample.hpp"
 #include "kernels_screen.hpp"
+#include "kernels_chain_pieces.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
 
@@ -1785,6 +1786,22 @@ struct Table : mp_table {
     if (!read_flag(false)) return;
     // some equation failed: the per-link verifier gives every link of ITS tables its exact status; the other tables' verdicts stand
     refine_groups(cv, gbad[0].p, false, Tq, Lq, false, false, 0, 0, false);
+  }
+  // chains of different lengths (kernels_chain_pieces.hpp): the G pieces of l links of one pass from the caller's table-major arrays into
+  // the link-major staging, in one launch; and the words of all passes back into the caller's table-major status array
+  size_t chain_piece_gather(const uint64_t* desc, size_t G, uint32_t l, const uint8_t* decks, const uint8_t* proofs, const uint8_t* keys,
+                            uint8_t* sdecks, uint8_t* sproofs, uint8_t* skeys) override {
+    const uint32_t dw = 2 * N * G_::PB / 16, pw = (uint32_t)(proof_size_bytes(m, n, G_::PB) / 16), kw = keys ? G_::PB / 16 : 0;
+    ChainPieceGatherArgs ga{desc, (const uint4*)decks, (const uint4*)proofs, (const uint4*)keys, (uint4*)sdecks, (uint4*)sproofs, (uint4*)skeys,
+                            (uint64_t)(l + 1) * G * dw, (uint64_t)l * G * pw, (uint64_t)l * G * kw, (uint32_t)G, dw, pw, kw};
+    const uint64_t W = ga.wd + ga.wp + ga.wk, ny = (W + CP_X_SPAN - 1) / CP_X_SPAN;
+    if (ny > 65535) throw std::runtime_error("chain verification: too many bytes in one pass for one launch");
+    MP_RUN(k_chain_piece_gather, C, (uint32_t)std::min<uint64_t>(W, CP_X_SPAN), (uint32_t)ny, ga);
+    return (size_t)W * 16;
+  }
+  void chain_piece_scatter(const uint64_t* desc, const uint64_t* pass, uint32_t passes, const int32_t* words, size_t total, int32_t* status) override {
+    ChainPieceScatterArgs sa{desc, pass, words, status, passes};
+    MP_RUN(k_chain_piece_scatter, C, (uint32_t)total, 1, sa);
   }
 
   // ---------------------------------------------------------------- group verification (round 4)

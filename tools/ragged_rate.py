@@ -6,7 +6,9 @@ drawn evenly from 2..10:
             mp_unmask_ragged_batch / mp_reveal_ragged_batch          against  9 x mp_unmask_batch / mp_reveal_batch
   seating   about 1 024 tables      mp_aggregate_keys_ragged_batch   against  9 x mp_aggregate_keys_batch
   chains    about 1 024 tables of 52 cards, one link per seat
-                                    mp_verify_shuffle_chain_ragged   against  9 x mp_verify_shuffle_chain
+                                    mp_verify_shuffle_chain_ragged   against  9 x mp_verify_shuffle_chain, in both decompositions
+                                    (mp_set_chain_pieces: w whole, b binary), and on device-resident inputs
+                                    mp_verify_shuffle_chain_ragged_dev  against  9 x mp_verify_shuffle_chain_dev (tags d)
 (a) mixed counts: the ragged call against the nine uniform calls.  (b) every count equal (6): the ragged call against the one uniform
 call -- the cost of the offsets path alone.  The buffers of both legs are prepared before; only the library calls are timed, each of
 which ends in a stream synchronise.  After one warm-up of both legs the legs alternate (and take turns in going first), `--reps`
@@ -20,6 +22,8 @@ import random
 import statistics
 import sys
 import time
+
+import torch  # noqa: F401  (before the library: torch ships a HIP runtime of its own, and the device leg of the chains keeps its buffers in it)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -220,7 +224,8 @@ def chaining(tag, links):
             decks[k].append(d[DB * i:DB * (i + 1)])
             proofs[k].append(p[t.proof_bytes * i:t.proof_bytes * (i + 1)])
     total = sum(links)
-    b_links, b_decks, b_prf = u32(links), buf(b"".join(b"".join(d) for d in decks)), buf(b"".join(b"".join(p) for p in proofs))
+    flat_decks, flat_prf = b"".join(b"".join(d) for d in decks), b"".join(b"".join(p) for p in proofs)
+    b_links, b_decks, b_prf = u32(links), buf(flat_decks), buf(flat_prf)
     o_st = words(total)
     groups = []
     for L, items in by_count(links):
@@ -234,8 +239,53 @@ def chaining(tag, links):
         for g in groups:
             chk(lib.mp_verify_shuffle_chain(h, len(g["items"]), g["L"], None, g["decks"], g["prf"], g["st"]))
     lines.append("%s chains: %d tables of %d cards, %d links, %d uniform call%s" % (tag, tables, N, total, len(groups), "s" if len(groups) > 1 else ""))
-    pair(tag + "c", "mp_verify_shuffle_chain_ragged", ragged, "%d x mp_verify_shuffle_chain" % len(groups), uniform, total, "links")
-    assert not any(o_st) and not any(v for g in groups for v in g["st"]), "a chain of the rate tool does not verify"
+    # the mode a table starts with: what the first call's stats say before anybody has set one
+    ragged()
+    if DEFAULT[0] is None:      # (read on the mixed lengths: where a cut saves no pass, as with equal lengths, the call makes none whatever is set)
+        DEFAULT[0] = chain_stats()[7]
+    default = DEFAULT[0]
+    for mode, name in PIECES:
+        chk(lib.mp_set_chain_pieces(h, mode))
+        pair(tag + "c" + name[0], "mp_verify_shuffle_chain_ragged, %s%s" % (name, " (default)" if mode == default else ""), ragged,
+             "%d x mp_verify_shuffle_chain" % len(groups), uniform, total, "links")
+        st = chain_stats()
+        lines.append("%-5s %s: cut made %s, %d passes, %d pieces, widest pass %d pieces, %.1f MB gathered on the device, %d bytes staged on the host" %
+                     (tag + "c" + name[0], name, PIECES[st[7]][1], st[0], st[1], st[6], st[4] / 1e6, st[5]))
+        assert not any(o_st) and not any(v for g in groups for v in g["st"]), "a chain of the rate tool does not verify"
+    # device-resident inputs: the ragged call against the uniform device calls on link-major arrays that are there already; every leg ends
+    # in mp_sync
+    dev = lambda raw: torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()      # noqa: E731
+    d_decks, d_prf = dev(flat_decks), dev(flat_prf)
+    d_st = torch.full((total,), 7, dtype=torch.int32, device="cuda")
+    for g in groups:
+        g["d_decks"], g["d_prf"] = dev(bytes(g["decks"])), dev(bytes(g["prf"]))
+        g["d_st"] = torch.full((g["L"] * len(g["items"]),), 7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def ragged_dev():
+        chk(lib.mp_verify_shuffle_chain_ragged_dev(h, tables, b_links, None, d_decks.data_ptr(), d_prf.data_ptr(), d_st.data_ptr()))
+        eng.sync()
+
+    def uniform_dev():
+        for g in groups:
+            chk(lib.mp_verify_shuffle_chain_dev(h, len(g["items"]), g["L"], None, g["d_decks"].data_ptr(), g["d_prf"].data_ptr(), g["d_st"].data_ptr()))
+        eng.sync()
+    for mode, name in PIECES:
+        chk(lib.mp_set_chain_pieces(h, mode))
+        pair(tag + "d" + name[0], "mp_verify_shuffle_chain_ragged_dev, %s%s" % (name, " (default)" if mode == default else ""), ragged_dev,
+             "%d x mp_verify_shuffle_chain_dev" % len(groups), uniform_dev, total, "links")
+        assert not d_st.any().item() and not any(g["d_st"].any().item() for g in groups), "a chain of the rate tool does not verify (device)"
+    chk(lib.mp_set_chain_pieces(h, default))
+
+
+PIECES = ((0, "whole"), (1, "binary"))
+DEFAULT = [None]      # the mode a table starts with
+
+
+def chain_stats():
+    out = (ctypes.c_uint64 * 8)()
+    chk(lib.mp_chain_ragged_stats(h, out))
+    return list(out)
 
 
 open_tables = (args.cards + 51) // 52
@@ -247,7 +297,7 @@ chaining("(a)", drawn(args.chain_tables, 3))
 opening("(b)", [EQUAL] * open_tables)
 seating("(b)", [EQUAL] * args.tables)
 chaining("(b)", [EQUAL] * args.chain_tables)
-lines.append("ragged / uniform, medians: " + "   ".join(ratios) + "   (r reveal, u unmask, s seating, c chains; outputs of every pair identical)")
+lines.append("ragged / uniform, medians: " + "   ".join(ratios) + "   (r reveal, u unmask, s seating, c chains from host buffers, d chains from device buffers, w / b pieces whole / binary; outputs of every pair identical)")
 print(lines[-1])
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "w") as f:
