@@ -270,6 +270,45 @@ class DLCardsT {
     return verify_mask_batch(MP_DEAL_REMASK, pp, shared_keys, key_index, original_cards.size(),
                              original_cards.empty() ? nullptr : original_cards[0].data(), remasked_cards, proofs);
   }
+  // The same four by index: the keys are the slots of a key set of the table bound now (key_set below), key_index[i] names a slot
+  // (mp_mask_batch_keyset, mp_verify_mask_batch_keyset); a card on an empty slot reads MP_ERR_BAD_ARGUMENT
+  DealtCards deal(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const mp_keyset* ks, const std::vector<uint32_t>& key_index,
+                  const std::vector<PublicKey>& cards, const std::vector<Scalar>& factors) {
+    return mask_batch_keyset(MP_DEAL_MASK, rng_seeds, ks, key_index, cards.size(), cards.empty() ? nullptr : cards[0].data(), factors);
+  }
+  std::vector<int32_t> verify_deal(const mp_keyset* ks, const std::vector<uint32_t>& key_index, const std::vector<PublicKey>& cards,
+                                   const std::vector<MaskedCard>& masked_cards, const std::vector<ZKProofMasking>& proofs) {
+    return verify_mask_batch_keyset(MP_DEAL_MASK, ks, key_index, cards.size(), cards.empty() ? nullptr : cards[0].data(), masked_cards, proofs);
+  }
+  DealtCards deal_remask(const std::vector<std::array<uint8_t, 32>>& rng_seeds, const mp_keyset* ks, const std::vector<uint32_t>& key_index,
+                         const std::vector<MaskedCard>& masked_cards, const std::vector<Scalar>& factors) {
+    return mask_batch_keyset(MP_DEAL_REMASK, rng_seeds, ks, key_index, masked_cards.size(), masked_cards.empty() ? nullptr : masked_cards[0].data(),
+                             factors);
+  }
+  std::vector<int32_t> verify_deal_remask(const mp_keyset* ks, const std::vector<uint32_t>& key_index, const std::vector<MaskedCard>& original_cards,
+                                          const std::vector<MaskedCard>& remasked_cards, const std::vector<ZKProofMasking>& proofs) {
+    return verify_mask_batch_keyset(MP_DEAL_REMASK, ks, key_index, original_cards.size(),
+                                    original_cards.empty() ? nullptr : original_cards[0].data(), remasked_cards, proofs);
+  }
+  // seating straight into a key set (mp_keyset_seat_ragged_batch): the sum of table k goes into slot slots[k] on the device;
+  // slot_status[k] is 0, the table's word, or MP_ERR_BAD_ENCODING for a sum that is the identity -- the slot is empty then
+  struct SeatedKeys {
+    AggregateKeys sums;
+    std::vector<int32_t> slot_status;
+  };
+  SeatedKeys seat(mp_keyset* ks, const std::vector<uint32_t>& slots, const std::vector<uint32_t>& players, const std::vector<PublicKey>& keys,
+                  const std::vector<ZKProofKeyOwnership>& proofs, const std::vector<std::array<uint8_t, 32>>& fs_init) {
+    const std::vector<uint32_t> first = ragged_first(players, players.size(), keys.size(), "seat");
+    if (proofs.size() != keys.size() || fs_init.size() != keys.size() || slots.size() != players.size())
+      throw CardProtocolError("seat: one proof and one digest per player, one slot per table");
+    const size_t tables = players.size();
+    SeatedKeys s{AggregateKeys{std::vector<PublicKey>(tables), std::vector<int32_t>(keys.size()), std::vector<int32_t>(tables)},
+                 std::vector<int32_t>(tables)};
+    if (mp_keyset_seat_ragged_batch(ks, tables, first.data(), slots.data(), keys[0].data(), proofs[0].data(), fs_init[0].data(), s.sums.keys[0].data(),
+                                    s.sums.player_status.data(), s.sums.table_status.data(), s.slot_status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return s;
+  }
   // tables x players, lane = table * players + seat; fs_init[lane] = Blake2s("Key Ownership Proof" || player_public_info) (mp_blake2s)
   AggregateKeys compute_aggregate_keys(const Parameters& pp, size_t players, const std::vector<PublicKey>& keys,
                                        const std::vector<ZKProofKeyOwnership>& proofs, const std::vector<std::array<uint8_t, 32>>& fs_init) {
@@ -484,6 +523,64 @@ class DLCardsT {
     if (!table_ || mp_set_chain_pieces(table_, mode) != MP_OK) throw CardProtocolError(table_ ? mp_last_error() : "set_chain_pieces: no table bound yet");
   }
 
+  // Key sets whose slots change (mpshuffle.h): a set of `capacity` empty slots on the table of `pp` (any_key: a key of pp, to bind the
+  // table).  It belongs to that table: key_set_close it before another Parameters value is bound.  key_set_update -> one status word
+  // per key: MP_OK, or MP_ERR_BAD_ENCODING for a refused key, whose slot is EMPTY afterwards; a malformed slots vector throws.
+  mp_keyset* key_set(const Parameters& pp, const PublicKey& any_key, size_t capacity) {
+    bind_any(pp, any_key);
+    mp_keyset* ks = nullptr;
+    if (mp_keyset_create_empty(table_, capacity, &ks) != MP_OK) throw CardProtocolError(mp_last_error());
+    return ks;
+  }
+  std::vector<int32_t> key_set_update(mp_keyset* ks, const std::vector<uint32_t>& slots, const std::vector<PublicKey>& keys) {
+    if (slots.empty() || keys.size() != slots.size()) throw CardProtocolError("key_set_update: at least one slot, one key per slot");
+    std::vector<int32_t> status(slots.size());
+    if (mp_keyset_update(ks, slots.size(), slots.data(), keys[0].data(), status.data()) != MP_OK) throw CardProtocolError(mp_last_error());
+    return status;
+  }
+  void key_set_update_dev(mp_keyset* ks, const std::vector<uint32_t>& slots, const void* d_keys, void* d_status) {
+    if (mp_keyset_update_dev(ks, slots.size(), slots.data(), d_keys, d_status) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  void key_set_clear(mp_keyset* ks, const std::vector<uint32_t>& slots) {
+    if (mp_keyset_clear(ks, slots.size(), slots.data()) != MP_OK) throw CardProtocolError(mp_last_error());
+  }
+  size_t key_set_live(const mp_keyset* ks) const { return mp_keyset_live(ks); }
+  void key_set_close(mp_keyset* ks) { mp_keyset_destroy(ks); }
+  // verify_shuffle_chains with the key of table t named as slot key_index[t] of a key set of the table bound now (Chain::shared_key is
+  // not read); every link of a table on an empty slot or past the set reads MP_ERR_BAD_ARGUMENT
+  std::vector<std::vector<int32_t>> verify_shuffle_chains(const Parameters& pp, const mp_keyset* ks, const std::vector<uint32_t>& key_index,
+                                                          const std::vector<Chain>& chains) {
+    const size_t N = (size_t)pp.m * pp.n, psz = mp_proof_size_curve(curve_, pp.m, pp.n);
+    if (chains.empty() || key_index.size() != chains.size()) throw CardProtocolError("verify_shuffle_chains: at least one table, one index per table");
+    std::vector<uint32_t> links;
+    std::vector<MaskedCard> decks;
+    std::vector<uint8_t> pf;
+    for (const Chain& ch : chains) {
+      if (ch.proofs.empty() || ch.decks.size() != ch.proofs.size() + 1)
+        throw CardProtocolError("verify_shuffle_chains: a chain is at least one link: links + 1 decks and one proof per link");
+      links.push_back((uint32_t)ch.proofs.size());
+      for (const std::vector<MaskedCard>& d : ch.decks) {
+        if (d.size() != N) throw CardProtocolError("decks must have m*n entries and proofs their wire length");
+        decks.insert(decks.end(), d.begin(), d.end());
+      }
+      for (const ZKProofShuffle& p : ch.proofs) {
+        if (p.size() != psz) throw CardProtocolError("decks must have m*n entries and proofs their wire length");
+        pf.insert(pf.end(), p.begin(), p.end());
+      }
+    }
+    std::vector<int32_t> status(pf.size() / psz);
+    if (!table_ || mp_verify_shuffle_chain_ragged_keyset(table_, ks, chains.size(), links.data(), key_index.data(), decks[0].data(), pf.data(),
+                                                         status.data()) != MP_OK)
+      throw CardProtocolError(table_ ? mp_last_error() : "verify_shuffle_chains: the key set's table is not bound");
+    std::vector<std::vector<int32_t>> out;
+    size_t o = 0;
+    for (uint32_t n : links) {
+      out.emplace_back(status.begin() + o, status.begin() + o + n);
+      o += n;
+    }
+    return out;
+  }
+
   mp_table* table() const { return table_; }   // for the batched / device-resident entry points of mpshuffle.h
   mp_pool_table* pool_table() const { return ptable_; }      // NULL without a device list
 
@@ -508,6 +605,26 @@ class DLCardsT {
     std::vector<int32_t> status(count);
     if (mp_verify_mask_batch(table_, kind, shared_keys.size(), shared_keys[0].data(), count, key_index.data(), inputs, masked_cards[0].data(),
                              proofs[0].data(), status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return status;
+  }
+  DealtCards mask_batch_keyset(int kind, const std::vector<std::array<uint8_t, 32>>& rng_seeds, const mp_keyset* ks, const std::vector<uint32_t>& key_index,
+                               size_t count, const uint8_t* inputs, const std::vector<Scalar>& factors) {
+    if (!count || !table_ || key_index.size() != count || factors.size() != count || rng_seeds.size() != count)
+      throw CardProtocolError("deal: the key set's table bound, at least one card; one slot, one factor and one seed per card");
+    DealtCards d{std::vector<MaskedCard>(count), std::vector<ZKProofMasking>(count), std::vector<int32_t>(count)};
+    if (mp_mask_batch_keyset(table_, ks, kind, count, key_index.data(), inputs, factors[0].data(), rng_seeds[0].data(), d.cards[0].data(),
+                             d.proofs[0].data(), d.status.data()) != MP_OK)
+      throw CardProtocolError(mp_last_error());
+    return d;
+  }
+  std::vector<int32_t> verify_mask_batch_keyset(int kind, const mp_keyset* ks, const std::vector<uint32_t>& key_index, size_t count,
+                                                const uint8_t* inputs, const std::vector<MaskedCard>& masked_cards,
+                                                const std::vector<ZKProofMasking>& proofs) {
+    if (!count || !table_ || key_index.size() != count || masked_cards.size() != count || proofs.size() != count)
+      throw CardProtocolError("verify_deal: the key set's table bound, at least one card; one slot, one masked card and one proof per card");
+    std::vector<int32_t> status(count);
+    if (mp_verify_mask_batch_keyset(table_, ks, kind, count, key_index.data(), inputs, masked_cards[0].data(), proofs[0].data(), status.data()) != MP_OK)
       throw CardProtocolError(mp_last_error());
     return status;
   }

@@ -207,6 +207,78 @@ int mp_shuffle_and_remask_batch_keyset_dev(mp_table* t, const mp_keyset* ks, siz
                                            void* d_out_decks, void* d_out_proofs, void* d_status);
 int mp_verify_shuffle_batch_keyset_dev(mp_table* t, const mp_keyset* ks, size_t B, const void* d_key_index, const void* d_decks,
                                        const void* d_shuffled_decks, const void* d_proofs, void* d_status);
+/* ---- key sets whose slots change: one table of thousands reseats between two hands --------------------------------------------
+ * A set is mp_keyset_size(ks) SLOTS, each live (it holds a key) or empty.  The set's device buffers are allocated once, for every
+ * slot, when it is created, and never move.  mp_keyset_create makes a set of n_keys live slots; mp_keyset_create_empty one of
+ * `capacity` empty slots (same limits).  mp_keyset_live: the number of live slots (takes the context's lock and waits for the
+ * updates in flight).
+ *
+ * mp_keyset_update[_dev] puts keys[i] (wire points; the _dev form: device memory) into slot slots[i], i < count, and builds the window
+ * tables of these `count` keys only, on the device, in slices of 1 024 keys whose staging the set keeps (a full slice:
+ * about 1.6 GB on the 256-bit curves for an update of that size or more, less for a smaller one).  Every key is validated on the
+ * device: canonical, on the curve, not the identity, in the prime-order subgroup -- whatever mp_set_subgroup_check says.
+ *   status[i] == MP_OK                slot slots[i] is live with key i
+ *   status[i] == MP_ERR_BAD_ENCODING  slot slots[i] is EMPTY, whatever it held before: a server that misses the word does not go on
+ *                                     serving the departed players' key under the table's index.  The other slots of the call are
+ *                                     not affected.
+ * mp_keyset_clear empties the named slots.
+ *
+ * `slots` is a HOST array in every form (the rule of `first` and `links` of the ragged calls): it is copied and the copy is checked
+ * before anything is enqueued.  count == 0, a slot >= mp_keyset_size(ks) or a slot named twice: the call returns MP_ERR_BAD_ARGUMENT,
+ * nothing is enqueued, the set is unchanged and no buffer of the caller's is touched.
+ *
+ * Ordering.  An update is enqueued on the context's stream behind everything the context holds on both lanes; pipelined verify calls
+ * whose screening verdicts are still unexamined (mp_set_pipeline) are completed first.  A call issued before the update sees the old
+ * keys, a call issued after it the new ones.  mp_keyset_update and mp_keyset_clear return when done; mp_keyset_update_dev returns when
+ * queued: d_keys must stay as it is, and d_status is final, after mp_sync.
+ *
+ * A proof that names an empty slot gets what an index >= mp_keyset_size(ks) gets: status MP_ERR_BAD_ARGUMENT for that proof, its
+ * outputs computed under slot 0 as they are for such an index, the other proofs of the batch untouched.  No kernel reads outside
+ * the set's buffers for any index. */
+int mp_keyset_create_empty(mp_table* t, size_t capacity, mp_keyset** out);
+size_t mp_keyset_live(const mp_keyset* ks);
+int mp_keyset_update(mp_keyset* ks, size_t count, const uint32_t* slots, const uint8_t* keys, int32_t* status);
+int mp_keyset_update_dev(mp_keyset* ks, size_t count, const uint32_t* slots, const void* d_keys, void* d_status);
+int mp_keyset_clear(mp_keyset* ks, size_t count, const uint32_t* slots);
+/* Keys by index where a round needs them.  Results are byte- and word-identical to the key-passing forms with the set's keys written out.
+ *
+ * mp_shuffle_and_remask_batch_seeded_keyset_dev is mp_shuffle_and_remask_batch_seeded_dev (below) with a set and one index per proof
+ * (d_key_index: B uint32, device memory) in place of d_keys; the keys' multiples come from the set's tables, as in
+ * mp_shuffle_and_remask_batch_keyset_dev.
+ *
+ * mp_verify_shuffle_chain_ragged_keyset[_dev] are mp_verify_shuffle_chain_ragged[_dev] (below) with ONE index per TABLE -- key_index: a
+ * host array of `tables` uint32 in the host form, a device array in the _dev form -- instead of one key per link: the per-link keys the
+ * chain verifier wants are written on the device.  A table whose index is >= mp_keyset_size(ks) or names an empty slot gets
+ * MP_ERR_BAD_ARGUMENT on every one of its links; the other tables are unaffected.  Both piece modes apply (mp_set_chain_pieces).
+ *
+ * mp_mask_batch_keyset, mp_verify_mask_batch_keyset and mp_verify_mask_batch_keyset_dev are mp_mask_batch, mp_verify_mask_batch and
+ * mp_verify_mask_batch_dev (below) with a set in place of `K` and `keys`: key_index[c] names a slot.  The prover takes its two products
+ * with the key, r pk for the masked card and w pk for the commitment, from the set's tables -- at most 32 table additions each and no
+ * window table of pk per card; the verifier reads the key from the set.  A card on an empty slot or past the set gets
+ * MP_ERR_BAD_ARGUMENT (and zero bytes from the prover), as a key index past `K` does.  mp_set_sigma_screen applies as to
+ * mp_verify_mask_batch.  A set's keys were tested for subgroup membership when they entered; the calls do not test them again.
+ *
+ * mp_keyset_seat_ragged_batch is mp_aggregate_keys_ragged_batch (below) whose sums go into the slots slots[k] of the set without leaving
+ * the device, through the validation and the table build of mp_keyset_update: player_status, table_status and out_keys (which may be
+ * NULL) are that call's words and bytes.  slot_status[k]: MP_OK, slot slots[k] is live under table k's aggregate key; table_status[k]
+ * where that is not 0, or MP_ERR_BAD_ENCODING where every proof is good and the sum is the identity (keys pk and -pk): the slot is
+ * EMPTY.  `slots` follows the rules of mp_keyset_update; uniform seating is first[k] = k * P. */
+int mp_mask_batch_keyset(mp_table* t, const mp_keyset* ks, int kind, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                         const uint8_t* factors, const uint8_t* prover_seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status);
+int mp_verify_mask_batch_keyset(mp_table* t, const mp_keyset* ks, int kind, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                                const uint8_t* masked, const uint8_t* proofs, int32_t* status);
+int mp_verify_mask_batch_keyset_dev(mp_table* t, const mp_keyset* ks, int kind, size_t C, const void* d_key_index, const void* d_inputs,
+                                    const void* d_masked, const void* d_proofs, void* d_status);
+int mp_keyset_seat_ragged_batch(mp_keyset* ks, size_t tables, const uint32_t* first, const uint32_t* slots, const uint8_t* keys,
+                                const uint8_t* proofs, const uint8_t* fs_init, uint8_t* out_keys, int32_t* player_status, int32_t* table_status,
+                                int32_t* slot_status);
+int mp_shuffle_and_remask_batch_seeded_keyset_dev(mp_table* t, const mp_keyset* ks, size_t B, const void* d_key_index, const void* d_decks,
+                                                  const void* d_seeds, void* d_out_decks, void* d_out_proofs, void* d_status, void* d_out_perms,
+                                                  void* d_out_factors);
+int mp_verify_shuffle_chain_ragged_keyset(mp_table* t, const mp_keyset* ks, size_t tables, const uint32_t* links, const uint32_t* key_index,
+                                          const uint8_t* decks, const uint8_t* proofs, int32_t* status);
+int mp_verify_shuffle_chain_ragged_keyset_dev(mp_table* t, const mp_keyset* ks, size_t tables, const uint32_t* links, const void* d_key_index,
+                                              const void* d_decks, const void* d_proofs, void* d_status);
 /* ---- chain verification: the shuffle chain of a card table verified as one equation -------------------------------------------
  * A table's deck passes through `links` shuffles (deck_{j+1} = output of link j [REF examples/round.rs:268-350]) and every one of
  * them is verified.  These entry points verify `tables` chains at once; decks: (links + 1) x tables decks, deck j of table t at index

@@ -21,6 +21,9 @@ SYMBOLS = [
     "mp_point_size", "mp_proof_size_curve", "mp_params_size_curve", "mp_set_merged_verify", "mp_set_subgroup_check", "mp_set_bucket_min", "mp_set_bucket_bits", "mp_set_bucket_split", "mp_set_validated", "mp_deck_validate_dev", "mp_set_chain_max_links", "mp_set_chain_group", "mp_set_chain_slice", "mp_chain_group_size", "mp_chain_last_slice", "mp_set_transcript_lanes", "mp_set_group_lanes", "mp_set_work_split", "mp_set_group_verify", "mp_group_size", "mp_set_group_refine", "mp_reverified_count", "mp_set_group_adapt", "mp_set_pipeline", "mp_set_plan_params", "mp_set_plan_thresholds", "mp_set_toom_cook", "mp_host_alloc", "mp_host_free", "mp_set_io_chunk", "mp_io_schedule","mp_shuffle_and_remask_batch_keys", "mp_table_create_params",
     "mp_verify_shuffle_batch_keys", "mp_shuffle_and_remask_batch_keys_dev", "mp_verify_shuffle_batch_keys_dev",
     "mp_keyset_create", "mp_keyset_destroy", "mp_keyset_size", "mp_shuffle_and_remask_batch_keyset_dev", "mp_verify_shuffle_batch_keyset_dev",
+    "mp_keyset_create_empty", "mp_keyset_live", "mp_keyset_update", "mp_keyset_update_dev", "mp_keyset_clear",
+    "mp_shuffle_and_remask_batch_seeded_keyset_dev", "mp_verify_shuffle_chain_ragged_keyset", "mp_verify_shuffle_chain_ragged_keyset_dev",
+    "mp_mask_batch_keyset", "mp_verify_mask_batch_keyset", "mp_verify_mask_batch_keyset_dev", "mp_keyset_seat_ragged_batch",
     "mp_setup", "mp_table_create", "mp_table_create_ex", "mp_table_window_bits", "mp_table_destroy", "mp_shuffle_and_remask", "mp_verify_shuffle",
     "mp_shuffle_and_remask_keyed", "mp_verify_shuffle_keyed", "mp_set_coalesce", "mp_coalesce_stats",
     "mp_shuffle_and_remask_batch", "mp_verify_shuffle_batch", "mp_shuffle_and_remask_batch_dev",
@@ -250,6 +253,19 @@ def bind(cdll):
     cdll.mp_keyset_destroy.restype = None
     cdll.mp_keyset_size.argtypes = [c.c_void_p]
     cdll.mp_keyset_size.restype = c.c_size_t
+    cdll.mp_keyset_create_empty.argtypes = [c.c_void_p, c.c_size_t, c.POINTER(c.c_void_p)]
+    cdll.mp_keyset_live.argtypes = [c.c_void_p]
+    cdll.mp_keyset_live.restype = c.c_size_t
+    cdll.mp_mask_batch_keyset.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_size_t, u32p, u8p, u8p, u8p, u8p, u8p, i32p]
+    cdll.mp_verify_mask_batch_keyset.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_size_t, u32p, u8p, u8p, u8p, i32p]
+    cdll.mp_verify_mask_batch_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_size_t] + [c.c_void_p] * 5
+    cdll.mp_keyset_seat_ragged_batch.argtypes = [c.c_void_p, c.c_size_t, u32p, u32p, u8p, u8p, u8p, u8p, i32p, i32p, i32p]
+    cdll.mp_keyset_update.argtypes = [c.c_void_p, c.c_size_t, u32p, u8p, i32p]
+    cdll.mp_keyset_update_dev.argtypes = [c.c_void_p, c.c_size_t, u32p, c.c_void_p, c.c_void_p]
+    cdll.mp_keyset_clear.argtypes = [c.c_void_p, c.c_size_t, u32p]
+    cdll.mp_shuffle_and_remask_batch_seeded_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t] + [c.c_void_p] * 8
+    cdll.mp_verify_shuffle_chain_ragged_keyset.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, u32p, u32p, u8p, u8p, i32p]
+    cdll.mp_verify_shuffle_chain_ragged_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, u32p] + [c.c_void_p] * 4
     cdll.mp_shuffle_and_remask_batch_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t] + [c.c_void_p] * 8
     cdll.mp_verify_shuffle_batch_keyset_dev.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t] + [c.c_void_p] * 5
     cdll.mp_verify_shuffle_chain.argtypes = [c.c_void_p, c.c_size_t, c.c_uint32, u8p, u8p, u8p, i32p]
@@ -561,16 +577,68 @@ class Engine:
 
 
 class KeySet:
-    """mp_keyset: fixed-base window tables of n aggregate keys of one Table (include/mpshuffle.h, "key sets")"""
+    """mp_keyset: fixed-base window tables of the aggregate keys of one Table, in slots that are live or empty
+    (include/mpshuffle.h, "key sets" and "key sets whose slots change").  KeySet(table, keys): one live slot per key;
+    KeySet(table, capacity=n): n empty slots"""
 
-    def __init__(self, table, keys):
+    def __init__(self, table, keys=None, capacity=None):
         self.table, self.lib = table, table.lib
-        if len(keys) == 0 or len(keys) % table.pb:
-            raise ValueError("keys: expected a whole number of %d-byte points" % table.pb)
-        self.size = len(keys) // table.pb
         h = ctypes.c_void_p()
-        table.eng._chk(self.lib.mp_keyset_create(table.h, self.size, _in(keys), ctypes.byref(h)))
+        if keys is None:
+            self.size = int(capacity)
+            table.eng._chk(self.lib.mp_keyset_create_empty(table.h, self.size, ctypes.byref(h)))
+        else:
+            if len(keys) == 0 or len(keys) % table.pb:
+                raise ValueError("keys: expected a whole number of %d-byte points" % table.pb)
+            self.size = len(keys) // table.pb
+            table.eng._chk(self.lib.mp_keyset_create(table.h, self.size, _in(keys), ctypes.byref(h)))
         self.h = h
+
+    @staticmethod
+    def _slots(slots):
+        return (ctypes.c_uint32 * max(len(slots), 1))(*slots)
+
+    def live(self):
+        """the number of live slots (waits for the updates in flight)"""
+        return int(self.lib.mp_keyset_live(self.h))
+
+    def seat(self, counts, slots, keys, proofs, fs_init, want_keys=True):
+        """mp_keyset_seat_ragged_batch: table k seats counts[k] players (their keys, proofs of key ownership and transcript digests, lane
+        by lane) and its aggregate key goes into slot slots[k] without leaving the device
+        -> (aggregate keys or None, player status, table status, slot status)"""
+        t = self.table
+        tables, lanes = len(counts), sum(counts)
+        if len(slots) != tables:
+            raise ValueError("slots: expected one slot per table")
+        t._need("keys", len(keys), lanes * t.pb)
+        t._need("proofs", len(proofs), lanes * (t.pb + 32))
+        t._need("fs_init", len(fs_init), lanes * 32)
+        first = [0]
+        for n in counts:
+            first.append(first[-1] + n)
+        out = (ctypes.c_uint8 * max(tables * t.pb, 1))() if want_keys else None
+        ps, ts, ss = (ctypes.c_int32 * max(lanes, 1))(), (ctypes.c_int32 * max(tables, 1))(), (ctypes.c_int32 * max(tables, 1))()
+        t.eng._chk(self.lib.mp_keyset_seat_ragged_batch(self.h, tables, (ctypes.c_uint32 * (tables + 1))(*first), self._slots(slots), _in(keys),
+                                                        _in(proofs), _in(fs_init), out, ps, ts, ss))
+        return (bytes(out)[:tables * t.pb] if want_keys else None), list(ps)[:lanes], list(ts)[:tables], list(ss)[:tables]
+
+    def update(self, slots, keys):
+        """slot slots[i] <- wire point i of keys (host bytes) -> status words: 0 = live with that key, MP_ERR_BAD_ENCODING = the key
+        was refused and the slot is EMPTY now.  A malformed slots list raises NativeError (MP_ERR_BAD_ARGUMENT): nothing has changed"""
+        if len(keys) != len(slots) * self.table.pb:
+            raise ValueError("keys: expected %d bytes" % (len(slots) * self.table.pb))
+        st = (ctypes.c_int32 * max(len(slots), 1))()
+        self.table.eng._chk(self.lib.mp_keyset_update(self.h, len(slots), self._slots(slots), _in(keys), st))
+        return list(st)[:len(slots)]
+
+    def update_dev(self, slots, d_keys, d_status):
+        """update over device arrays (slots is a host list): queued behind everything the context holds; d_status is final after
+        Engine.sync()"""
+        self.table.eng._chk(self.lib.mp_keyset_update_dev(self.h, len(slots), self._slots(slots), d_keys, d_status))
+
+    def clear(self, slots):
+        """the named slots are empty afterwards"""
+        self.table.eng._chk(self.lib.mp_keyset_clear(self.h, len(slots), self._slots(slots)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -710,12 +778,41 @@ class Table:
         """keys: n wire points back to back (host bytes) -> KeySet (close() it before the table)"""
         return KeySet(self, keys)
 
+    def keyset_empty(self, capacity):
+        """a KeySet of `capacity` empty slots, to be filled by KeySet.update / update_dev"""
+        return KeySet(self, capacity=capacity)
+
     def shuffle_and_remask_batch_keyset_dev(self, ks, B, d_key_index, d_decks, d_factors, d_perms, d_seeds, d_out_decks, d_out_proofs, d_status):
         self.eng._chk(self.lib.mp_shuffle_and_remask_batch_keyset_dev(self.h, ks.h, B, d_key_index, d_decks, d_factors, d_perms, d_seeds,
                                                                       d_out_decks, d_out_proofs, d_status))
 
     def verify_shuffle_batch_keyset_dev(self, ks, B, d_key_index, d_decks, d_shuffled, d_proofs, d_status):
         self.eng._chk(self.lib.mp_verify_shuffle_batch_keyset_dev(self.h, ks.h, B, d_key_index, d_decks, d_shuffled, d_proofs, d_status))
+
+    def shuffle_and_remask_batch_seeded_keyset_dev(self, ks, B, d_key_index, d_decks, d_seeds, d_out_decks, d_out_proofs, d_status,
+                                                   d_out_perms=None, d_out_factors=None):
+        """shuffle_and_remask_batch_seeded_dev with key d_key_index[b] of the key set for proof b"""
+        self.eng._chk(self.lib.mp_shuffle_and_remask_batch_seeded_keyset_dev(self.h, ks.h, B, d_key_index, d_decks, d_seeds, d_out_decks,
+                                                                             d_out_proofs, d_status, d_out_perms, d_out_factors))
+
+    def verify_shuffle_chain_ragged_keyset(self, ks, links, key_index, decks, proofs):
+        """verify_shuffle_chain_ragged with ONE key-set index per table (key_index[t]) instead of a key per link -> status words; every
+        link of a table whose index names no key reads MP_ERR_BAD_ARGUMENT"""
+        tables, total = len(links), sum(links)
+        if len(key_index) != tables:
+            raise ValueError("key_index: expected one index per table")
+        self._need("decks", len(decks), (total + tables) * self.N * self.cb)
+        self._need("proofs", len(proofs), total * self.proof_bytes)
+        st = (ctypes.c_int32 * max(total, 1))()
+        lk = (ctypes.c_uint32 * max(tables, 1))(*links)
+        ki = (ctypes.c_uint32 * max(tables, 1))(*key_index)
+        self.eng._chk(self.lib.mp_verify_shuffle_chain_ragged_keyset(self.h, ks.h, tables, lk, ki, _in(decks), _in(proofs), st))
+        return list(st)[:total]
+
+    def verify_shuffle_chain_ragged_keyset_dev(self, ks, links, d_key_index, d_decks, d_proofs, d_status):
+        """the same over device arrays (16-byte aligned; d_key_index: one uint32 per table); `links` is a host list"""
+        lk = (ctypes.c_uint32 * max(len(links), 1))(*links)
+        self.eng._chk(self.lib.mp_verify_shuffle_chain_ragged_keyset_dev(self.h, ks.h, len(links), lk, d_key_index, d_decks, d_proofs, d_status))
 
     def shuffle_and_remask_batch_keys_dev(self, B, d_keys, d_decks, d_factors, d_perms, d_seeds, d_out_decks, d_out_proofs, d_status):
         self.eng._chk(self.lib.mp_shuffle_and_remask_batch_keys_dev(self.h, B, d_keys, d_decks, d_factors, d_perms, d_seeds,
@@ -980,6 +1077,33 @@ class Table:
         st = (ctypes.c_int32 * max(C, 1))()
         self.eng._chk(self.lib.mp_verify_mask_batch(self.h, kind, K, _in(keys), C, ki, _in(inputs), _in(masked), _in(proofs), st))
         return list(st)[:C]
+
+    def mask_batch_keyset(self, ks, kind, key_index, inputs, factors, seeds):
+        """mask_batch with the keys named as slots of a key set (key_index[c]) -> (masked cards, proofs, status)"""
+        C = len(key_index)
+        isz, psz = (self.cb if kind == self.DEAL_REMASK else self.pb), 2 * self.pb + 32
+        self._need("inputs", len(inputs), C * isz)
+        self._need("masking factors", len(factors), C * 32)
+        self._need("prover seeds", len(seeds), C * 32)
+        ki = (ctypes.c_uint32 * max(C, 1))(*key_index)
+        out, prf, st = (ctypes.c_uint8 * max(C * self.cb, 1))(), (ctypes.c_uint8 * max(C * psz, 1))(), (ctypes.c_int32 * max(C, 1))()
+        self.eng._chk(self.lib.mp_mask_batch_keyset(self.h, ks.h, kind, C, ki, _in(inputs), _in(factors), _in(seeds), out, prf, st))
+        return bytes(out)[:C * self.cb], bytes(prf)[:C * psz], list(st)[:C]
+
+    def verify_mask_batch_keyset(self, ks, kind, key_index, inputs, masked, proofs):
+        """verify_mask_batch with the keys named as slots of a key set -> one status word per card"""
+        C = len(key_index)
+        self._need("inputs", len(inputs), C * (self.cb if kind == self.DEAL_REMASK else self.pb))
+        self._need("masked cards", len(masked), C * self.cb)
+        self._need("proofs", len(proofs), C * (2 * self.pb + 32))
+        ki = (ctypes.c_uint32 * max(C, 1))(*key_index)
+        st = (ctypes.c_int32 * max(C, 1))()
+        self.eng._chk(self.lib.mp_verify_mask_batch_keyset(self.h, ks.h, kind, C, ki, _in(inputs), _in(masked), _in(proofs), st))
+        return list(st)[:C]
+
+    def verify_mask_batch_keyset_dev(self, ks, kind, C, d_key_index, d_inputs, d_masked, d_proofs, d_status):
+        """the same with device pointers; d_status is final after Engine.sync()"""
+        self.eng._chk(self.lib.mp_verify_mask_batch_keyset_dev(self.h, ks.h, kind, C, d_key_index, d_inputs, d_masked, d_proofs, d_status))
 
     def verify_mask_batch_dev(self, kind, K, d_keys, C, d_key_index, d_inputs, d_masked, d_proofs, d_status):
         """the same with device pointers (d_inputs may be a prover's d_out_decks); d_status is final after Engine.sync()"""

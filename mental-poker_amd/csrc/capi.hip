@@ -272,6 +272,13 @@ void mp_table_destroy(mp_table* t) {
       }
       rt::event_destroy(t->ragged_first_up);
     }
+    if (t->ck_off_up) {
+      try {
+        rt::event_sync(t->ck_off_up);
+      } catch (...) {
+      }
+      rt::event_destroy(t->ck_off_up);
+    }
     if (t->cp_plan_up) {
       try {
         rt::event_sync(t->cp_plan_up);
@@ -595,11 +602,107 @@ void mp_keyset_destroy(mp_keyset* ks) {
   if (!ks) return;
   try {
     MP_ENTER(ks->owner->ctx);
+    if (ks->up_slots_up) {
+      try {
+        rt::event_sync(ks->up_slots_up);
+      } catch (...) {
+      }
+      rt::event_destroy(ks->up_slots_up);
+    }
     delete ks;
   } catch (...) {
   }
 }
 size_t mp_keyset_size(const mp_keyset* ks) { return ks ? ks->K : 0; }
+int mp_keyset_create_empty(mp_table* t, size_t capacity, mp_keyset** out) {
+  if (!t || !capacity || !out) return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_create_empty: bad argument");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  std::unique_ptr<mp_keyset> ks(new mp_keyset());
+  ks->owner = t;
+  const int rc = t->keyset_build_empty(*ks, capacity);
+  if (rc != MP_OK) return rc;
+  *out = ks.release();
+  return MP_OK;
+  MP_CATCH
+}
+size_t mp_keyset_live(const mp_keyset* ks) {
+  if (!ks) return 0;
+  try {
+    MP_ENTER(ks->owner->ctx);
+    std::vector<uint32_t> live(ks->K);
+    rt::Stream s = ks->owner->ctx->stream;
+    rt::d2h(live.data(), ks->live.p, ks->K * 4, s);      // behind every update the stream holds
+    rt::stream_sync(s);
+    size_t n = 0;
+    for (uint32_t v : live) n += v != 0u;
+    return n;
+  } catch (...) {
+    return 0;
+  }
+}
+// The slots array of an update (the rule of `first` in the ragged calls, ragged_take below): copied into the set's own vector, checked
+// THERE -- count >= 1, every slot below the capacity, no slot twice -- and uploaded from there.  Nothing has been enqueued and the set
+// is as it was when this fails.  Holds the context's lock.  -> the device array, or nullptr for a malformed one
+static const uint32_t* keyset_take(mp_keyset* ks, size_t count, const uint32_t* slots) {
+  if (count < 1 || count > ks->K) return nullptr;
+  rt::Stream s = ks->owner->ctx->stream;
+  if (ks->up_slots_up)
+    rt::event_sync(ks->up_slots_up);
+  else
+    ks->up_slots_up = rt::event_create();
+  std::vector<uint32_t>& h = ks->up_slots_host;
+  h.assign(slots, slots + count);
+  std::vector<uint32_t> sorted(h);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.back() >= ks->K) return nullptr;
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return nullptr;
+  ks->up_slots.alloc(count, s, false);
+  rt::h2d(ks->up_slots.p, h.data(), count * 4, s);
+  rt::event_record(ks->up_slots_up, s);
+  return ks->up_slots.p;
+}
+static const char* const KEYSET_SLOTS = "1 <= count, every slot below the capacity of the set, no slot twice";
+int mp_keyset_update_dev(mp_keyset* ks, size_t count, const uint32_t* slots, const void* d_keys, void* d_status) {
+  if (!ks || !slots || !d_keys || !d_status) return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_update_dev: null argument");
+  MP_TRY
+  mp_table* t = ks->owner;
+  MP_ENTER(t->ctx);
+  const uint32_t* d_slots = keyset_take(ks, count, slots);
+  if (!d_slots) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_keyset_update_dev: ") + KEYSET_SLOTS);
+  t->keyset_update(*ks, count, d_slots, (const uint8_t*)d_keys, (int32_t*)d_status);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_keyset_update(mp_keyset* ks, size_t count, const uint32_t* slots, const uint8_t* keys, int32_t* status) {
+  if (!ks || !slots || !keys || !status) return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_update: null argument");
+  MP_TRY
+  mp_table* t = ks->owner;
+  MP_ENTER(t->ctx);
+  const uint32_t* d_slots = keyset_take(ks, count, slots);
+  if (!d_slots) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_keyset_update: ") + KEYSET_SLOTS);
+  rt::Stream s = t->ctx->stream;
+  ks->up_keys.alloc(count * t->point_bytes, s, false);
+  ks->up_status.alloc(count, s, false);
+  rt::h2d(ks->up_keys.p, keys, count * t->point_bytes, s);
+  t->keyset_update(*ks, count, d_slots, ks->up_keys.p, ks->up_status.p);
+  rt::d2h(status, ks->up_status.p, count * 4, s);
+  rt::stream_sync(s);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_keyset_clear(mp_keyset* ks, size_t count, const uint32_t* slots) {
+  if (!ks || !slots) return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_clear: null argument");
+  MP_TRY
+  mp_table* t = ks->owner;
+  MP_ENTER(t->ctx);
+  const uint32_t* d_slots = keyset_take(ks, count, slots);
+  if (!d_slots) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_keyset_clear: ") + KEYSET_SLOTS);
+  t->keyset_update(*ks, count, d_slots, nullptr, nullptr);
+  rt::stream_sync(t->ctx->stream);
+  return MP_OK;
+  MP_CATCH
+}
 int mp_shuffle_and_remask_batch_keyset_dev(mp_table* t, const mp_keyset* ks, size_t B, const void* d_key_index, const void* d_decks,
                                            const void* d_masking_factors, const void* d_permutations, const void* d_prover_seeds,
                                            void* d_out_decks, void* d_out_proofs, void* d_status) {
@@ -864,6 +967,74 @@ int mp_verify_shuffle_chain_ragged(mp_table* t, size_t tables, const uint32_t* l
     rt::h2d(t->cp_in_keys.p, shared_keys, total * pb, s);
   }
   const int rc = chain_ragged_passes(t, passes, shared_keys ? t->cp_in_keys.p : nullptr, t->cp_in_decks.p, t->cp_in_proofs.p, t->cp_in_status.p);
+  if (rc != MP_OK) return rc;
+  rt::d2h(status, t->cp_in_status.p, total * 4, s);
+  rt::stream_sync(s);
+  return MP_OK;
+  MP_CATCH
+}
+// ---- chains by index: one slot of a key set per TABLE; the per-link keys the passes want are written on the device
+// the link offsets of the tables, from the validated copy of the links (chain_ragged_take) -> the device array [tables + 1]
+static const uint32_t* chain_keyset_offsets(mp_table* t, size_t tables) {
+  rt::Stream s = t->ctx->stream;
+  if (t->ck_off_up)
+    rt::event_sync(t->ck_off_up);
+  else
+    t->ck_off_up = rt::event_create();
+  std::vector<uint32_t>& h = t->ck_off_host;
+  h.assign(tables + 1, 0);
+  for (size_t k = 0; k < tables; ++k) h[k + 1] = h[k] + t->cp_links[k];      // (less than 2^31 in all)
+  t->ck_off.alloc(tables + 1, s, false);
+  rt::h2d(t->ck_off.p, h.data(), (tables + 1) * 4, s);
+  rt::event_record(t->ck_off_up, s);
+  return t->ck_off.p;
+}
+static int chain_keyset_passes(mp_table* t, const mp_keyset* ks, size_t tables, const std::vector<ChainPass>& passes, const uint32_t* d_kidx,
+                               const uint8_t* d_decks, const uint8_t* d_proofs, int32_t* d_status) {
+  const size_t total = (size_t)t->cp_stats[3];
+  const uint32_t* d_off = chain_keyset_offsets(t, tables);
+  t->ck_keys.alloc(total * t->point_bytes, t->ctx->stream, false);
+  t->keyset_chain_keys(*ks, tables, d_kidx, d_off, t->ck_keys.p);
+  const int rc = chain_ragged_passes(t, passes, t->ck_keys.p, d_decks, d_proofs, d_status);
+  if (rc != MP_OK) return rc;
+  t->keyset_chain_status(*ks, tables, d_kidx, d_off, d_status);
+  return MP_OK;
+}
+int mp_verify_shuffle_chain_ragged_keyset_dev(mp_table* t, const mp_keyset* ks, size_t tables, const uint32_t* links, const void* d_key_index,
+                                              const void* d_decks, const void* d_proofs, void* d_status) {
+  if (!t || !ks || ks->owner != t || !tables || !links || !d_key_index || !d_decks || !d_proofs || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged_keyset_dev: bad argument (the key set must belong to this table)");
+  if (((uintptr_t)d_decks | (uintptr_t)d_proofs) & 15u)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged_keyset_dev: the device arrays must be 16-byte aligned");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  std::vector<ChainPass> passes;
+  if (int bad = chain_ragged_take(t, tables, links, passes)) return bad;
+  NoPipeline nopipe(t);
+  return chain_keyset_passes(t, ks, tables, passes, (const uint32_t*)d_key_index, (const uint8_t*)d_decks, (const uint8_t*)d_proofs,
+                             (int32_t*)d_status);
+  MP_CATCH
+}
+int mp_verify_shuffle_chain_ragged_keyset(mp_table* t, const mp_keyset* ks, size_t tables, const uint32_t* links, const uint32_t* key_index,
+                                          const uint8_t* decks, const uint8_t* proofs, int32_t* status) {
+  if (!t || !ks || ks->owner != t || !tables || !links || !key_index || !decks || !proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_shuffle_chain_ragged_keyset: bad argument (the key set must belong to this table)");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  std::vector<ChainPass> passes;
+  if (int bad = chain_ragged_take(t, tables, links, passes)) return bad;
+  NoPipeline nopipe(t);
+  rt::Stream s = t->ctx->stream;
+  const size_t pb = t->point_bytes, deck_bytes = (size_t)2 * t->N * pb, psz = proof_size_bytes(t->m, t->n, (uint32_t)pb);
+  const size_t total = (size_t)t->cp_stats[3];
+  t->cp_in_decks.alloc((total + tables) * deck_bytes, s, false);
+  t->cp_in_proofs.alloc(total * psz, s, false);
+  t->cp_in_status.alloc(total, s, false);
+  t->ck_idx.alloc(tables, s, false);
+  rt::h2d(t->cp_in_decks.p, decks, (total + tables) * deck_bytes, s);
+  rt::h2d(t->cp_in_proofs.p, proofs, total * psz, s);
+  rt::h2d(t->ck_idx.p, key_index, tables * 4, s);
+  const int rc = chain_keyset_passes(t, ks, tables, passes, t->ck_idx.p, t->cp_in_decks.p, t->cp_in_proofs.p, t->cp_in_status.p);
   if (rc != MP_OK) return rc;
   rt::d2h(status, t->cp_in_status.p, total * 4, s);
   rt::stream_sync(s);
@@ -1603,6 +1774,41 @@ int mp_verify_mask_batch_dev(mp_table* t, int kind, size_t K, const void* d_keys
   return MP_OK;
   MP_CATCH
 }
+// dealing by index: the keys are those of a key set, key_index names slots
+int mp_mask_batch_keyset(mp_table* t, const mp_keyset* ks, int kind, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                         const uint8_t* factors, const uint8_t* prover_seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) {
+  if (!t || !ks || ks->owner != t || !key_index || !inputs || !factors || !prover_seeds || !out_masked || !out_proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_mask_batch_keyset: bad argument (the key set must belong to this table)");
+  if (!deal_shape_ok(kind, ks->K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_mask_batch_keyset: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->mask_host(kind, ks->K, nullptr, C, key_index, inputs, factors, prover_seeds, out_masked, out_proofs, status, ks);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_verify_mask_batch_keyset(mp_table* t, const mp_keyset* ks, int kind, size_t C, const uint32_t* key_index, const uint8_t* inputs,
+                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) {
+  if (!t || !ks || ks->owner != t || !key_index || !inputs || !masked || !proofs || !status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_mask_batch_keyset: bad argument (the key set must belong to this table)");
+  if (!deal_shape_ok(kind, ks->K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_verify_mask_batch_keyset: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->verify_mask_host(kind, ks->K, nullptr, C, key_index, inputs, masked, proofs, status, ks);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_verify_mask_batch_keyset_dev(mp_table* t, const mp_keyset* ks, int kind, size_t C, const void* d_key_index, const void* d_inputs,
+                                    const void* d_masked, const void* d_proofs, void* d_status) {
+  if (!t || !ks || ks->owner != t || !d_key_index || !d_inputs || !d_masked || !d_proofs || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_verify_mask_batch_keyset_dev: bad argument (the key set must belong to this table)");
+  if (!deal_shape_ok(kind, ks->K, C)) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_verify_mask_batch_keyset_dev: ") + DEAL_SHAPE);
+  MP_TRY
+  MP_ENTER(t->ctx);
+  t->verify_mask_dev(kind, ks->K, nullptr, C, (const uint32_t*)d_key_index, (const uint8_t*)d_inputs, (const uint8_t*)d_masked,
+                     (const uint8_t*)d_proofs, (int32_t*)d_status, ks);
+  return MP_OK;
+  MP_CATCH
+}
 int mp_aggregate_keys_batch(mp_table* t, size_t tables, uint32_t P, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                             uint8_t* out_keys, int32_t* player_status, int32_t* table_status) {
   if (!t || !keys || !proofs || !fs_init || !out_keys || !player_status || !table_status)
@@ -1625,6 +1831,25 @@ int mp_aggregate_keys_ragged_batch(mp_table* t, size_t tables, const uint32_t* f
   if (!d_first)
     return fail(MP_ERR_BAD_ARGUMENT, "mp_aggregate_keys_ragged_batch: first[0] == 0, first strictly increasing, first[tables] <= 1 048 576");
   t->aggregate_keys_host(tables, 0, keys, proofs, fs_init, out_keys, player_status, table_status, d_first, t->ragged_first_host[tables]);
+  return MP_OK;
+  MP_CATCH
+}
+// seating straight into a key set: the sums of mp_aggregate_keys_ragged_batch go into the slots `slots` without leaving the device
+int mp_keyset_seat_ragged_batch(mp_keyset* ks, size_t tables, const uint32_t* first, const uint32_t* slots, const uint8_t* keys,
+                                const uint8_t* proofs, const uint8_t* fs_init, uint8_t* out_keys, int32_t* player_status, int32_t* table_status,
+                                int32_t* slot_status) {
+  if (!ks || !first || !slots || !keys || !proofs || !fs_init || !player_status || !table_status || !slot_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_seat_ragged_batch: null argument");
+  MP_TRY
+  mp_table* t = ks->owner;
+  MP_ENTER(t->ctx);
+  const uint32_t* d_slots = keyset_take(ks, tables, slots);
+  if (!d_slots) return fail(MP_ERR_BAD_ARGUMENT, std::string("mp_keyset_seat_ragged_batch: ") + KEYSET_SLOTS);
+  const uint32_t* d_first = ragged_take(t, tables, first, DEAL_MAX_LANES);
+  if (!d_first)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_seat_ragged_batch: first[0] == 0, first strictly increasing, first[tables] <= 1 048 576");
+  t->aggregate_keys_host(tables, 0, keys, proofs, fs_init, out_keys, player_status, table_status, d_first, t->ragged_first_host[tables], ks, d_slots,
+                         slot_status);
   return MP_OK;
   MP_CATCH
 }
@@ -1676,6 +1901,26 @@ int mp_shuffle_and_remask_batch_seeded_dev(mp_table* t, size_t B, const void* d_
   t->sample_dev(B, (const uint8_t*)d_seeds, (uint32_t)N, (uint32_t)N, rho, perm);
   t->prove_dev(B, (const uint8_t*)d_decks, rho, perm, (const uint8_t*)d_seeds, (uint8_t*)d_out_decks, (uint8_t*)d_out_proofs,
                (int32_t*)d_status, (const uint8_t*)d_keys);
+  return MP_OK;
+  MP_CATCH
+}
+int mp_shuffle_and_remask_batch_seeded_keyset_dev(mp_table* t, const mp_keyset* ks, size_t B, const void* d_key_index, const void* d_decks,
+                                                  const void* d_seeds, void* d_out_decks, void* d_out_proofs, void* d_status, void* d_out_perms,
+                                                  void* d_out_factors) {
+  if (!t || !ks || ks->owner != t || !B || !d_key_index || !d_decks || !d_seeds || !d_out_decks || !d_out_proofs || !d_status)
+    return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch_seeded_keyset_dev: bad argument (the key set must belong to this table)");
+  if (B > SAMPLE_MAX_LANES) return fail(MP_ERR_BAD_ARGUMENT, "mp_shuffle_and_remask_batch_seeded_keyset_dev: at most 1 048 576 proofs per call");
+  MP_TRY
+  MP_ENTER(t->ctx);
+  rt::Stream s = t->ctx->stream;
+  const size_t N = t->N;
+  if (!d_out_factors) t->seeded_rho.alloc(B * N * 32, s, false);
+  if (!d_out_perms) t->seeded_perm.alloc(B * N, s, false);
+  uint8_t* rho = d_out_factors ? (uint8_t*)d_out_factors : t->seeded_rho.p;
+  uint32_t* perm = d_out_perms ? (uint32_t*)d_out_perms : t->seeded_perm.p;
+  t->sample_dev(B, (const uint8_t*)d_seeds, (uint32_t)N, (uint32_t)N, rho, perm);
+  t->prove_dev(B, (const uint8_t*)d_decks, rho, perm, (const uint8_t*)d_seeds, (uint8_t*)d_out_decks, (uint8_t*)d_out_proofs,
+               (int32_t*)d_status, nullptr, ks, (const uint32_t*)d_key_index);
   return MP_OK;
   MP_CATCH
 }

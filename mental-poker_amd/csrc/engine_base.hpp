@@ -217,8 +217,24 @@ struct mp_keyset {
   mp::DevBuf<uint32_t> wire;     // [K][point_bytes / 4]: the keys as they came (gathered per proof for the transcript / the key's own terms)
   mp::DevBuf<uint32_t> FB;       // [K][windows][entries] affine points (the layout of the table context's own fixed-base tables)
   uint32_t bits = 0, windows = 0, entries = 0;
+  // Slots that change (mp_keyset_create_empty / _update / _clear; kernels_keyset.hpp).  K is the capacity: wire and FB are allocated
+  // once for all of it and never move.  live: [K] words, 1 = the slot holds a key; the kernels that name a key by index read it.
+  // INVARIANT: a refused or cleared slot keeps whatever tables it had in FB -- only its live word and its wire words are zeroed.  Every
+  // reader of FB goes through keyset_slot (kernels_msm.hpp), which sends an empty slot to slot 0 and reports it; read FB no other way.
+  mp::DevBuf<uint32_t> live;
+  // the slots array of an update: the caller's host array is copied into up_slots_host, checked THERE and uploaded from there (as
+  // mp_table::ragged_first_host); the copy is not overwritten or freed before the event behind its upload has passed
+  mp::DevBuf<uint32_t> up_slots;
+  std::vector<uint32_t> up_slots_host;
+  mp::rt::Event up_slots_up = nullptr;
+  // the staging of one build slice (engine_core.hpp KEYSET_UPDATE_SLICE): the keys as affine points, the passes' intermediates and the
+  // finished tables before they are scattered into their slots.  Sized for the largest update so far, at most one slice; they grow only
+  mp::DevBuf<uint32_t> up_pts, up_WJ, up_W, up_EJ, up_scratch, up_tab;
+  // the device copies of the host form's arrays (mp_keyset_update)
+  mp::DevBuf<uint8_t> up_keys;
+  mp::DevBuf<int32_t> up_status;
 };
-struct mp_coalescer;             // request coalescing of the single-proof host-buffer entry points (capi.hip, mp_set_coalesce)
+struct mp_coalescer;            // request coalescing of the single-proof host-buffer entry points (capi.hip, mp_set_coalesce)
 struct mp_table {
   mp_ctx* ctx = nullptr;
   mp_coalescer* co = nullptr;     // created with the table by capi.hip and gone with it; off until mp_set_coalesce
@@ -264,6 +280,20 @@ struct mp_table {
   virtual void verify_dev(size_t B, const uint8_t* decks, const uint8_t* shuf, const uint8_t* proofs, int32_t* status,
                           const uint8_t* keys = nullptr, const mp_keyset* ks = nullptr, const uint32_t* kidx = nullptr) = 0;
   virtual int keyset_build(mp_keyset& ks, size_t K, const uint8_t* keys_host) = 0;
+  // slots that change: a set of K empty slots; d_slots (count distinct slots below K, device memory) take the wire keys d_keys, one
+  // status word each -- or are emptied (d_keys == nullptr: d_status is not written).  Enqueued on the context's stream behind both lanes
+  virtual int keyset_build_empty(mp_keyset& ks, size_t K) = 0;
+  virtual void keyset_update(mp_keyset& ks, size_t count, const uint32_t* d_slots, const uint8_t* d_keys, int32_t* d_status) = 0;
+  // chains by index (kernels_keyset.hpp): the key of table t's slot d_kidx[t] written once per link into d_keys, rows d_off[t] ..
+  // d_off[t + 1] - 1; and, behind the verifier, MP_ERR_BAD_ARGUMENT on every link of a table that named no key
+  virtual void keyset_chain_keys(const mp_keyset& ks, size_t tables, const uint32_t* d_kidx, const uint32_t* d_off, uint8_t* d_keys) = 0;
+  virtual void keyset_chain_status(const mp_keyset& ks, size_t tables, const uint32_t* d_kidx, const uint32_t* d_off, int32_t* d_status) = 0;
+  // their arrays: the link offsets of the tables (from the validated copy of the caller's links; host copy and upload event as
+  // ragged_first_host), the expanded keys, and the device copy of the host form's indices
+  mp::DevBuf<uint32_t> ck_off, ck_idx;
+  std::vector<uint32_t> ck_off_host;
+  mp::rt::Event ck_off_up = nullptr;
+  mp::DevBuf<uint8_t> ck_keys;
   // chain verification: T tables x L links, decks [(L + 1)][T], proofs / status / keys [L][T] (device memory)
   virtual void verify_chain_dev(size_t T, uint32_t L, const uint8_t* decks, const uint8_t* proofs, int32_t* status,
                                 const uint8_t* keys = nullptr) = 0;
@@ -319,14 +349,16 @@ struct mp_table {
   // dealing and seating (kernels_deal.hpp): K keys, C cards with a key index each, kind = MP_DEAL_MASK | MP_DEAL_REMASK; mask_host /
   // verify_mask_host / aggregate_keys_host take host buffers, verify_mask_dev device pointers
   virtual void mask_host(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
-                         const uint8_t* factors, const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) = 0;
+                         const uint8_t* factors, const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status,
+                         const mp_keyset* ks = nullptr) = 0;      // ks: the keys are the set's (keys, K are not read), key_index names slots
   virtual void verify_mask_host(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
-                                const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
+                                const uint8_t* masked, const uint8_t* proofs, int32_t* status, const mp_keyset* ks = nullptr) = 0;
   virtual void verify_mask_dev(int kind, size_t K, const uint8_t* keys, size_t C, const uint32_t* key_index, const uint8_t* inputs,
-                               const uint8_t* masked, const uint8_t* proofs, int32_t* status) = 0;
+                               const uint8_t* masked, const uint8_t* proofs, int32_t* status, const mp_keyset* ks = nullptr) = 0;
   virtual void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init,
                                    uint8_t* out_keys, int32_t* player_status, int32_t* table_status, const uint32_t* first = nullptr,
-                                   size_t lanes = 0) = 0;
+                                   size_t lanes = 0, mp_keyset* seat_ks = nullptr, const uint32_t* d_slots = nullptr,
+                                   int32_t* slot_status = nullptr) = 0;      // seat_ks: the sums go into its slots d_slots (out_keys may be null)
   // the offsets array of the ragged calls (capi.hip ragged_take): the caller's array is copied into ragged_first_host, validated THERE and
   // uploaded from there into ragged_first, so what the kernels read is what was validated whatever the caller does with its array
   // after the call returns, and whatever kind of memory it lies in.  ragged_first_up is recorded behind the upload: the host copy is not

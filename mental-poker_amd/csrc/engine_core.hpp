@@ -10,6 +10,7 @@
 #include "kernels_sample.hpp"
 #include "kernels_screen.hpp"
 #include "kernels_chain_pieces.hpp"
+#include "kernels_keyset.hpp"
 #include "serialize_host.hpp"
 #include "setup_host.hpp"
 
@@ -537,13 +538,20 @@ struct Table : mp_table {
     W.alloc(nwinpts * G_::PW, s);
     EJ.alloc(nent * G_::JW, s);
     scratch.alloc(nent * G_::FW, s);
-    FbWinArgs wa{pts, WJ.p, gh, h2};
-    MP_RUN(k_fb_windows, C, nb, 1, wa);
-    normalize_flat(WJ.p, W.p, scratch.p, nwinpts);
-    FbFillArgs fa{W.p, EJ.p, gh};
-    MP_RUN(k_fb_fill, C, (uint32_t)nwinpts, 1, fa);
-    normalize_flat(EJ.p, out, scratch.p, nent);
+    enqueue_narrow_tables(pts, nb, gh, h2, out, WJ.p, W.p, EJ.p, scratch.p);
     rt::stream_sync(s);
+  }
+  // the passes alone, on buffers of the caller's: [nb * windows] Jacobian and affine window bases, [nb * windows * entries] Jacobian
+  // entries and as many field elements of inversion scratch.  Nothing is allocated or waited for
+  void enqueue_narrow_tables(const uint32_t* pts, uint32_t nb, const FbGeom& gh, uint32_t h2, uint32_t* out, uint32_t* WJ, uint32_t* W,
+                             uint32_t* EJ, uint32_t* scratch) {
+    const size_t nwinpts = (size_t)nb * gh.windows, nent = nwinpts * gh.entries;
+    FbWinArgs wa{pts, WJ, gh, h2};
+    MP_RUN(k_fb_windows, C, nb, 1, wa);
+    normalize_flat(WJ, W, scratch, nwinpts);
+    FbFillArgs fa{W, EJ, gh};
+    MP_RUN(k_fb_fill, C, (uint32_t)nwinpts, 1, fa);
+    normalize_flat(EJ, out, scratch, nent);
   }
   void build_fixed_tables(uint32_t nb) {
     rt::Stream s = ctx->stream;
@@ -599,6 +607,8 @@ struct Table : mp_table {
     ks.bits = g8.bits; ks.windows = g8.windows; ks.entries = g8.entries;
     const size_t per_key = (size_t)g8.windows * g8.entries * G_::PW;
     ks.FB.alloc(K * per_key, s, false);
+    const std::vector<uint32_t> all_live(K, 1u);
+    ks.live.upload(all_live, s);      // (the stream is waited for below)
     const size_t slice = 2048;
     for (size_t k0 = 0; k0 < K; k0 += slice) {
       const uint32_t kc = (uint32_t)std::min(slice, K - k0);
@@ -607,11 +617,68 @@ struct Table : mp_table {
     rt::stream_sync(s);
     return MP_OK;
   }
+  // ---- slots that change (kernels_keyset.hpp).  An update builds the tables of ITS keys only, in slices of KEYSET_UPDATE_SLICE keys
+  // whose staging the set keeps: 1 024 keys are 0.5 GB of tables, 0.8 GB of Jacobian entries and 0.27 GB of inversion scratch on the
+  // 256-bit curves, and 32 768 lanes for k_fb_fill.  Nothing here waits for the stream once the staging is as large as the call needs.
+#ifdef MP_EXP_KS_SLICE      // the emulator's second library (tools/hostemu: make KS_SLICE=4): an update of slice + 1 keys in seconds
+  static constexpr size_t KEYSET_UPDATE_SLICE = MP_EXP_KS_SLICE;
+#else
+  static constexpr size_t KEYSET_UPDATE_SLICE = 1024;
+#endif
+  int keyset_build_empty(mp_keyset& ks, size_t K) override {
+    rt::Stream s = ctx->stream;
+    const FbGeom g8{8u, ((uint32_t)R::BITS + 7u) / 8u, 255u};
+    if (K == 0 || K * (size_t)g8.windows * g8.entries >= ((size_t)1 << 32)) return fail(MP_ERR_BAD_ARGUMENT, "mp_keyset_create_empty: 1 .. 500 000 slots");
+    ks.K = K;
+    ks.bits = g8.bits; ks.windows = g8.windows; ks.entries = g8.entries;
+    // zero words are the identity, as wire key and as table entry: what slot 0 lends to a proof that names no key is defined
+    ks.wire.alloc(K * (G_::PB / 4), s);
+    ks.FB.alloc(K * (size_t)g8.windows * g8.entries * G_::PW, s);
+    ks.live.alloc(K, s);
+    rt::stream_sync(s);
+    return MP_OK;
+  }
+  void keyset_update(mp_keyset& ks, size_t count, const uint32_t* d_slots, const uint8_t* d_keys, int32_t* d_status) override {
+    // a pipelined verify call whose verdict is still unexamined holds a pointer to the set, and its second pass would read the new keys:
+    // complete those first.  That also waits for the verify lane; the prove lane IS the stream the update is enqueued on
+    flush();
+    rt::Stream s = ctx->stream;
+    const FbGeom g8{ks.bits, ks.windows, ks.entries};
+    const size_t per_key = (size_t)g8.windows * g8.entries * G_::PW;
+    if (d_keys) {
+      const size_t kc = std::min(count, KEYSET_UPDATE_SLICE), nwinpts = kc * g8.windows, nent = nwinpts * g8.entries;
+      ks.up_pts.alloc(kc * G_::PW, s, false);
+      ks.up_WJ.alloc(nwinpts * G_::JW, s, false);
+      ks.up_W.alloc(nwinpts * G_::PW, s, false);
+      ks.up_EJ.alloc(nent * G_::JW, s, false);
+      ks.up_scratch.alloc(nent * G_::FW, s, false);
+      ks.up_tab.alloc(kc * per_key, s, false);
+    }
+    for (size_t k0 = 0; k0 < count; k0 += KEYSET_UPDATE_SLICE) {
+      const uint32_t kc = (uint32_t)std::min(KEYSET_UPDATE_SLICE, count - k0);
+      KeysetSlotsArgs sa{d_keys ? d_keys + k0 * G_::PB : nullptr, d_slots + k0, ks.wire.p, ks.live.p, ks.up_pts.p,
+                         d_keys ? d_status + k0 : nullptr};
+      MP_RUN(k_keyset_slots, C, kc, 1, sa);
+      if (!d_keys) continue;
+      enqueue_narrow_tables(ks.up_pts.p, kc, g8, 8u, ks.up_tab.p, ks.up_WJ.p, ks.up_W.p, ks.up_EJ.p, ks.up_scratch.p);
+      KeysetScatterArgs ca{reinterpret_cast<const uint4*>(ks.up_tab.p), reinterpret_cast<uint4*>(ks.FB.p), d_slots + k0, ks.live.p,
+                           (uint32_t)(per_key / 4)};
+      MP_RUN(k_keyset_scatter, C, ca.words, kc, ca);
+    }
+  }
+  void keyset_chain_keys(const mp_keyset& ks, size_t tables, const uint32_t* d_kidx, const uint32_t* d_off, uint8_t* d_keys) override {
+    KeysetChainKeysArgs a{ks.wire.p, ks.live.p, d_kidx, d_off, reinterpret_cast<uint32_t*>(d_keys), (uint32_t)ks.K};
+    MP_RUN(k_keyset_chain_keys, C, (uint32_t)tables, G_::PB / 4, a);
+  }
+  void keyset_chain_status(const mp_keyset& ks, size_t tables, const uint32_t* d_kidx, const uint32_t* d_off, int32_t* d_status) override {
+    KeysetChainStatusArgs a{ks.live.p, d_kidx, d_off, d_status, (uint32_t)ks.K};
+    MP_RUN(k_keyset_chain_status, C, (uint32_t)tables, 1, a);
+  }
   DevBuf<uint32_t> ks_keys_main, ks_keys_vlane;      // the wire keys of a batch, gathered from a key set (one buffer per lane)
   const uint8_t* gather_keys(uint32_t B, const mp_keyset* ks, const uint32_t* kidx, int32_t* status, bool vlane = false) {
     DevBuf<uint32_t>& ks_keys = vlane ? ks_keys_vlane : ks_keys_main;
     ks_keys.alloc((size_t)B * (G_::PB / 4), ctx->stream, false);
-    GatherKeysArgs ga{ks->wire.p, kidx, ks_keys.p, status, (uint32_t)ks->K};
+    GatherKeysArgs ga{ks->wire.p, kidx, ks_keys.p, status, (uint32_t)ks->K, ks->live.p};
     MP_RUN(k_gather_keys, C, B, G_::PB / 4, ga);
     return reinterpret_cast<const uint8_t*>(ks_keys.p);
   }
@@ -1037,6 +1104,7 @@ struct Table : mp_table {
         ra.kidx = kidx;
         ra.kg = FbGeom{kset->bits, kset->windows, kset->entries};
         ra.nkeys = (uint32_t)kset->K;
+        ra.live = kset->live.p;
       } else if (keyed) {
         // the proof's key -> window bases 2^(5w) pk -> their 16-entry tables; signed digits of the masking factors
         LoadPointsArgs ka{keys, w.P.p, w.status.p, w.Bpad, 1, l.pk};
@@ -1095,7 +1163,7 @@ struct Table : mp_table {
     if (keyed) {      // tau_k pk, k < 2m, from the key's own tables (the proof's, or its key set's): finished partial sums of the E_k
       KeyTermsArgs ka{w.S.p, w.J.p, w.Bpad, l.metau, q.pplan.jkey, kset ? 2u : 1u, w.T.p, key_t_first, nwin,
                       kset ? kset->FB.p : nullptr, kidx, kset ? FbGeom{kset->bits, kset->windows, kset->entries} : FbGeom{8, 32, 255},
-                      kset ? (uint32_t)kset->K : 0u};
+                      kset ? (uint32_t)kset->K : 0u, kset ? kset->live.p : nullptr};
       MP_RUN(k_key_terms, C, B, 2 * m, ka);
     }
     if (overlap) {
@@ -2593,6 +2661,8 @@ struct Table : mp_table {
     PhaseDev vdev, pdev1, pdev2, sdev;
     Phase kph1, kph2;               // key generation: pk = sk G | the commitment r G
     PhaseDev kdev1, kdev2;
+    Phase qph1, qph2;               // dealing by index: x G | r G alone, the products with pk come from the key set's tables
+    PhaseDev qdev1, qdev2;
     uint32_t nJ = 0, nD = 0, nT = 0;
     uint32_t fs_seed[2][8];         // Blake2s("Masking Proof"), Blake2s("Remasking Proof")  [REF mod.rs:80-81]
     Workspace w;
@@ -2646,6 +2716,20 @@ struct Table : mp_table {
         pb.normalize(l.A, 2);
       }
       {
+        PhaseBuilder pb(deal.qph1, np, FCHUNK, VCHUNK);
+        pb.begin(l.a);
+        pb.fixed(l.x, fb.G());
+        pb.end();
+        pb.normalize(l.a, 2);
+      }
+      {
+        PhaseBuilder pb(deal.qph2, np, FCHUNK, VCHUNK);
+        pb.begin(l.A);
+        pb.fixed(l.r, fb.G());
+        pb.end();
+        pb.normalize(l.A, 2);
+      }
+      {
         PhaseBuilder pb(deal.sph, np, FCHUNK, VCHUNK);      // z G - c pk - A
         pb.begin(sl.chk);
         pb.fixed(sl.z, fb.G());
@@ -2673,7 +2757,7 @@ struct Table : mp_table {
         throw std::logic_error("deal plan: the phases do not share the table of pk");
       deal.pph2.tables.clear();
       deal.nJ = np;
-      for (const Phase* ph : {&deal.vph, &deal.pph1, &deal.pph2, &deal.sph, &deal.kph1, &deal.kph2}) {
+      for (const Phase* ph : {&deal.vph, &deal.pph1, &deal.pph2, &deal.sph, &deal.kph1, &deal.kph2, &deal.qph1, &deal.qph2}) {
         deal.nD = std::max(deal.nD, ph->n_dslots);
         deal.nT = std::max(deal.nT, ph->n_tslots);
       }
@@ -2683,6 +2767,8 @@ struct Table : mp_table {
       deal.sdev.upload(deal.sph, s);
       deal.kdev1.upload(deal.kph1, s);
       deal.kdev2.upload(deal.kph2, s);
+      deal.qdev1.upload(deal.qph1, s);
+      deal.qdev2.upload(deal.qph2, s);
       const char* names[2] = {"Masking Proof", "Remasking Proof"};
       for (int k = 0; k < 2; ++k) {
         Blake2sState st;
@@ -2699,8 +2785,14 @@ struct Table : mp_table {
     deal.fs.alloc((size_t)deal.w.cap * 32, s, false);
     rt::dzero(deal.w.status.p, (size_t)deal.w.Bpad * 4, s);
   }
-  DealStmtArgs deal_stmt_args(int kind, size_t K, const uint8_t* keys, const uint32_t* key_index, const uint8_t* inputs) {
+  DealStmtArgs deal_stmt_args(int kind, size_t K, const uint8_t* keys, const uint32_t* key_index, const uint8_t* inputs,
+                              const mp_keyset* ks = nullptr) {
     DealStmtArgs a{};
+    if (ks) {      // dealing by index: the set's own copy of the wire keys, validated when they entered
+      keys = reinterpret_cast<const uint8_t*>(ks->wire.p);
+      K = ks->K;
+      a.live = ks->live.p;
+    }
     Workspace& w = deal.w;
     a.P = w.P.p; a.J = w.J.p; a.S = w.S.p; a.status = w.status.p;
     a.keys = keys; a.key_index = key_index; a.inputs = inputs;
@@ -2713,20 +2805,20 @@ struct Table : mp_table {
   }
   // every pointer a device pointer; everything is enqueued on the context's stream
   void verify_mask_dev(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs,
-                       const uint8_t* masked, const uint8_t* proofs, int32_t* status) override {
+                       const uint8_t* masked, const uint8_t* proofs, int32_t* status, const mp_keyset* ks) override {
     const uint32_t B = (uint32_t)C_;
     deal_prepare(B);
     Workspace& w = deal.w;
     const DealLay d = make_deal_lay();
     const SigmaLay& l = d.s;
-    DealStmtArgs sa = deal_stmt_args(kind, K, keys, key_index, inputs);
+    DealStmtArgs sa = deal_stmt_args(kind, K, keys, key_index, inputs, ks);
     sa.masked = masked;
     MP_RUN(k_deal_stmt, C, B, 4, sa);
     // the publics a_i = masked_i - in_i become affine before the transcript absorbs them: one batched inversion for both slots
     normalize_flat(w.J.p + j_off<C>(l.a, w.Bpad, 0), w.P.p + p_off<C>(l.a, w.Bpad, 0), w.NS.p, (size_t)2 * w.Bpad);
     SigmaIoArgs io{const_cast<uint8_t*>(proofs), w.S.p, w.P.p, w.status.p, l, w.Bpad};
     MP_RUN(k_sigma_load, C, B, 3, io);
-    check_subgroup(w, B, l.g + 1, 1);      // the key (G is the table's own; the differences of subgroup points are subgroup points)
+    if (!ks) check_subgroup(w, B, l.g + 1, 1);      // the key (G is the table's own; the differences of subgroup points are subgroup points; a set's keys were tested when they entered)
     check_subgroup(w, B, l.A, 6);          // commitments, input card and masked card are consecutive P slots
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 0};
@@ -2736,33 +2828,35 @@ struct Table : mp_table {
       SigmaVerdictArgs va{w.J.p, w.status.p, l, w.Bpad, 6};
       MP_RUN(k_sigma_verdict, C, B, 1, va);
     }
-    DealFinishArgs fin{w.status.p, key_index, status, nullptr, nullptr, (uint32_t)K};
+    DealFinishArgs fin{w.status.p, key_index, status, nullptr, nullptr, sa.K, sa.live};
     MP_RUN(k_deal_finish, C, B, 1, fin);
   }
   static size_t deal_input_bytes(int kind) { return (kind == MP_DEAL_REMASK ? 2 : 1) * (size_t)G_::PB; }
   void verify_mask_host(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs,
-                        const uint8_t* masked, const uint8_t* proofs, int32_t* status) override {
+                        const uint8_t* masked, const uint8_t* proofs, int32_t* status, const mp_keyset* ks) override {
     rt::Stream s = ctx->stream;
     const size_t psz = 2 * (size_t)G_::PB + 32, isz = deal_input_bytes(kind);
     DevBuf<uint8_t> dk, din, dm, dp;
     DevBuf<uint32_t> dki;
     DevBuf<int32_t> dst;
+    if (ks) K = 0;
     dk.alloc(K * G_::PB, s, false); din.alloc(C_ * isz, s, false); dm.alloc(C_ * 2 * G_::PB, s, false); dp.alloc(C_ * psz, s, false);
     dki.alloc(C_, s, false); dst.alloc(C_, s, false);
-    rt::h2d(dk.p, keys, K * G_::PB, s);
+    if (K) rt::h2d(dk.p, keys, K * G_::PB, s);
     rt::h2d(din.p, inputs, C_ * isz, s);
     rt::h2d(dm.p, masked, C_ * 2 * G_::PB, s);
     rt::h2d(dp.p, proofs, C_ * psz, s);
     rt::h2d(dki.p, key_index, C_ * 4, s);
-    verify_mask_dev(kind, K, dk.p, C_, dki.p, din.p, dm.p, dp.p, dst.p);
+    verify_mask_dev(kind, K, dk.p, C_, dki.p, din.p, dm.p, dp.p, dst.p, ks);
     rt::d2h(status, dst.p, C_ * 4, s);
     rt::stream_sync(s);
   }
   // (x G, x pk) first: the hedged nonce hashes the whole statement, the publics included (k_sigma_init)
   void mask_host(int kind, size_t K, const uint8_t* keys, size_t C_, const uint32_t* key_index, const uint8_t* inputs, const uint8_t* factors,
-                 const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status) override {
+                 const uint8_t* seeds, uint8_t* out_masked, uint8_t* out_proofs, int32_t* status, const mp_keyset* ks) override {
     rt::Stream s = ctx->stream;
     const uint32_t B = (uint32_t)C_;
+    if (ks) K = 0;
     const size_t psz = 2 * (size_t)G_::PB + 32, isz = deal_input_bytes(kind);
     deal_prepare(B);
     Workspace& w = deal.w;
@@ -2773,31 +2867,49 @@ struct Table : mp_table {
     DevBuf<int32_t> dst;
     dk.alloc(K * G_::PB, s, false); din.alloc(C_ * isz, s, false); dx.alloc(C_ * 32, s, false); dseed.alloc(C_ * 32, s, false);
     dm.alloc(C_ * 2 * G_::PB, s, false); dpf.alloc(C_ * psz, s, false); dki.alloc(C_, s, false); dst.alloc(C_, s, false);
-    rt::h2d(dk.p, keys, K * G_::PB, s);
+    if (K) rt::h2d(dk.p, keys, K * G_::PB, s);
     rt::h2d(din.p, inputs, C_ * isz, s);
     rt::h2d(dx.p, factors, C_ * 32, s);
     rt::h2d(dseed.p, seeds, C_ * 32, s);
     rt::h2d(dki.p, key_index, C_ * 4, s);
-    DealStmtArgs sa = deal_stmt_args(kind, K, dk.p, dki.p, din.p);
+    DealStmtArgs sa = deal_stmt_args(kind, K, dk.p, dki.p, din.p, ks);
     sa.factors = dx.p;
     MP_RUN(k_deal_stmt, C, B, 4, sa);
-    check_subgroup(w, B, l.g + 1, 1);      // the key and the input card, as the sigma calls test bases and publics
+    if (!ks) check_subgroup(w, B, l.g + 1, 1);      // the key and the input card, as the sigma calls test bases and publics
     check_subgroup(w, B, d.in, 2);
-    run_phase(deal.pdev1, w, B);
+    // by index: x pk and r pk are sums of entries of the set's tables (k_deal_key_term) beside x G and r G from the table's own; the
+    // phase's normalisation takes both slots
+    auto key_term = [&](uint32_t s_slot, uint32_t j_slot) {
+      DealKeyTermArgs ka{w.S.p, w.J.p, w.Bpad, s_slot, j_slot, ks->FB.p, dki.p, ks->live.p, FbGeom{ks->bits, ks->windows, ks->entries}, (uint32_t)ks->K};
+      MP_RUN(k_deal_key_term, C, B, 1, ka);
+    };
+    if (ks) {
+      run_phase(deal.qdev1, w, B, PH_ALL & ~PH_NORM);
+      key_term(l.x, l.a + 1);
+      run_phase(deal.qdev1, w, B, PH_NORM);
+    } else {
+      run_phase(deal.pdev1, w, B);
+    }
     DealAddArgs aa{w.P.p, w.J.p, d, w.Bpad};
     MP_RUN(k_deal_add, C, B, 2, aa);
     normalize_flat(w.J.p + j_off<C>(d.out, w.Bpad, 0), w.P.p + p_off<C>(d.out, w.Bpad, 0), w.NS.p, (size_t)2 * w.Bpad);
     const FsDev f{w.stage.p, w.seed.p, w.Bpad};
     SigmaInitArgs ia{w.S.p, dseed.p, l, w.Bpad, f, w.P.p, deal.fs.p};
     MP_RUN(k_sigma_init, C, B, 1, ia);
-    run_phase(deal.pdev2, w, B);             // (its table list is empty: the table of pk is the first phase's)
+    if (ks) {
+      run_phase(deal.qdev2, w, B, PH_ALL & ~PH_NORM);
+      key_term(l.r, l.A + 1);
+      run_phase(deal.qdev2, w, B, PH_NORM);
+    } else {
+      run_phase(deal.pdev2, w, B);             // (its table list is empty: the table of pk is the first phase's)
+    }
     SigmaFsArgs fa{f, w.S.p, w.P.p, deal.fs.p, l, 1};
     MP_RUN(k_sigma_fs, C, B, 1, fa);
     SigmaIoArgs io{dpf.p, w.S.p, w.P.p, w.status.p, l, w.Bpad};
     MP_RUN(k_sigma_store, C, B, 3, io);
     StorePointsArgs so{dm.p, w.P.p, w.Bpad, 2, d.out};
     MP_RUN(k_store_points, C, B, 2, so);
-    DealFinishArgs fin{w.status.p, dki.p, dst.p, dm.p, dpf.p, (uint32_t)K};
+    DealFinishArgs fin{w.status.p, dki.p, dst.p, dm.p, dpf.p, sa.K, sa.live};
     MP_RUN(k_deal_finish, C, B, 1, fin);
     rt::d2h(out_masked, dm.p, C_ * 2 * G_::PB, s);
     rt::d2h(out_proofs, dpf.p, C_ * psz, s);
@@ -2806,7 +2918,8 @@ struct Table : mp_table {
   }
   // seating: lane = table * seats + seat, or with an offsets array the lanes first[table] .. first[table + 1] - 1
   void aggregate_keys_host(size_t tables, uint32_t seats, const uint8_t* keys, const uint8_t* proofs, const uint8_t* fs_init, uint8_t* out_keys,
-                           int32_t* player_status, int32_t* table_status, const uint32_t* first, size_t lanes) override {
+                           int32_t* player_status, int32_t* table_status, const uint32_t* first, size_t lanes, mp_keyset* seat_ks,
+                           const uint32_t* d_slots, int32_t* slot_status) override {
     rt::Stream s = ctx->stream;
     const uint32_t Tn = (uint32_t)tables, B = first ? (uint32_t)lanes : Tn * seats;
     const size_t psz = (size_t)G_::PB + 32;
@@ -2839,7 +2952,17 @@ struct Table : mp_table {
     normalize_flat(deal.sumJ.p, deal.sumP.p, deal.scratch.p, Tn);
     StorePointsArgs so{dout.p, deal.sumP.p, Tn, 1, 0};      // (the identity is zero bytes on the wire: a refused table's key)
     MP_RUN(k_store_points, C, Tn, 1, so);
-    rt::d2h(out_keys, dout.p, (size_t)Tn * G_::PB, s);
+    DevBuf<int32_t> dss;
+    if (seat_ks) {
+      // the sums never leave HBM: they enter the set through the validation and the table build of an update.  A refused table's sum
+      // is the identity, which the validation refuses: its slot is emptied, as for keys that cancel
+      dss.alloc(Tn, s, false);
+      keyset_update(*seat_ks, Tn, d_slots, dout.p, dss.p);
+      KeysetSeatStatusArgs ss{dts.p, dss.p};
+      MP_RUN(k_keyset_seat_status, C, Tn, 1, ss);
+      rt::d2h(slot_status, dss.p, (size_t)Tn * 4, s);
+    }
+    if (out_keys) rt::d2h(out_keys, dout.p, (size_t)Tn * G_::PB, s);
     rt::d2h(player_status, dps.p, (size_t)B * 4, s);
     rt::d2h(table_status, dts.p, (size_t)Tn * 4, s);
     rt::stream_sync(s);

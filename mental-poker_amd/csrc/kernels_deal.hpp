@@ -43,6 +43,7 @@ struct DealStmtArgs {
   uint32_t fs_seed[8];
   DealLay l;
   uint32_t Bpad, K, g_base, remask;
+  const uint32_t* live = nullptr;   // dealing by index (mp_mask_batch_keyset): keys are a key set's wire keys, [K] words, 1 = the slot holds a key
 };
 // x = card, y = 0: g_0 = G, the digest and (proving) the factor as the witness; 1: g_1 = keys[key_index]; 2, 3: component y - 2 of the
 // input card and (verifying) of the masked card with their difference, Jacobian, in the J slot of a_{y-2}.  A lane whose key index is
@@ -54,7 +55,7 @@ MP_HD void body_deal_stmt(const DealStmtArgs& a, uint32_t b, uint32_t y) {
   constexpr uint32_t PB = Geo<C>::PB;
   const SigmaLay& l = a.l.s;
   const uint32_t ki = a.key_index[b];
-  const bool known = ki < a.K;
+  const bool known = ki < a.K && (!a.live || a.live[ki] != 0u);
   if (!known) status_fail(a.status, b, ST_BAD_ARGUMENT);
   bool ok = true;
   if (y == 0) {
@@ -120,13 +121,15 @@ struct DealFinishArgs {
   uint8_t* out_masked;        // [C] c0 || c1 (proving) or nullptr
   uint8_t* out_proofs;        // [C] proofs (proving) or nullptr
   uint32_t K;
+  const uint32_t* live = nullptr;   // as DealStmtArgs::live
 };
 // the status word of a card, MP_ERR_BAD_ARGUMENT for a key index past the list whatever the later tests wrote; a prover lane with a
 // word that is not 0 gives zero bytes
 template <class C>
 MP_HD void body_deal_finish(const DealFinishArgs& a, uint32_t b, uint32_t y) {
   constexpr uint32_t CW = 2 * Geo<C>::PB / 4, QW = (2 * Geo<C>::PB + 32) / 4;
-  const int32_t st = a.key_index[b] < a.K ? a.wstatus[b] : ST_BAD_ARGUMENT;
+  const uint32_t ki = a.key_index[b];
+  const int32_t st = ki < a.K && (!a.live || a.live[ki] != 0u) ? a.wstatus[b] : ST_BAD_ARGUMENT;
   a.status[b] = st;
   if (st != 0 && a.out_masked) {
     uint32_t* m = reinterpret_cast<uint32_t*>(a.out_masked) + (size_t)b * CW;

@@ -194,7 +194,15 @@ struct RemaskArgs {
   const uint32_t* kidx; // [B]
   FbGeom kg;
   uint32_t nkeys;
+  const uint32_t* live = nullptr;   // [nkeys] 1 = the slot holds a key (mp_keyset_update / mp_keyset_clear), or null = all of them
 };
+// the slot proof b names, or slot 0 for an index past the set or an empty slot (ok = false: k_gather_keys reports it through the status
+// word): nothing outside the set's buffers is ever read
+MP_HD uint32_t keyset_slot(const uint32_t* kidx, uint32_t b, uint32_t nkeys, const uint32_t* live, bool& ok) {
+  const uint32_t key = kidx[b];
+  ok = key < nkeys && (!live || live[key] != 0u);
+  return ok ? key : 0u;
+}
 // y = 2*i + component
 template <class C>
 MP_HD void body_remask(const RemaskArgs& a, uint32_t b, uint32_t y) {
@@ -207,8 +215,8 @@ MP_HD void body_remask(const RemaskArgs& a, uint32_t b, uint32_t y) {
   const uint32_t base = comp ? a.base_pk : a.base_G;
   Xyzz<C> acc = xyzz_inf<C>();
   if (a.keyed == 2 && comp) {
-    uint32_t key = a.kidx[b];
-    if (key >= a.nkeys) key = 0;      // reported through the status word (k_gather_keys)
+    bool named;
+    const uint32_t key = keyset_slot(a.kidx, b, a.nkeys, a.live, named);
 #pragma unroll 1
     for (uint32_t w = 0; w < a.kg.windows; ++w) {
       const uint32_t d = fb_digit(k, a.kg, w);
@@ -258,6 +266,7 @@ struct KeyTermsArgs {
   const uint32_t* kidx;
   FbGeom kg;
   uint32_t nkeys;
+  const uint32_t* live = nullptr;   // as RemaskArgs::live
 };
 template <class C>
 MP_HD void body_key_terms(const KeyTermsArgs& a, uint32_t b, uint32_t y) {
@@ -266,8 +275,8 @@ MP_HD void body_key_terms(const KeyTermsArgs& a, uint32_t b, uint32_t y) {
   fe_to_canonical<R>(ld_fe<R>(a.S + s_off(a.s_first + y, a.Bpad, b)), k);
   Xyzz<C> acc = xyzz_inf<C>();
   if (a.keyed == 2) {
-    uint32_t key = a.kidx[b];
-    if (key >= a.nkeys) key = 0;      // reported through the status word (k_gather_keys)
+    bool named;
+    const uint32_t key = keyset_slot(a.kidx, b, a.nkeys, a.live, named);
 #pragma unroll 1
     for (uint32_t w = 0; w < a.kg.windows; ++w) {
       const uint32_t d = fb_digit(k, a.kg, w);
@@ -301,15 +310,14 @@ struct GatherKeysArgs {
   uint32_t* out;          // [B][PB / 4]
   int32_t* status;
   uint32_t nkeys;
+  const uint32_t* live = nullptr;   // as RemaskArgs::live
 };
 template <class C>
 MP_HD void body_gather_keys(const GatherKeysArgs& a, uint32_t b, uint32_t y) {
   constexpr uint32_t W = Geo<C>::PB / 4;
-  uint32_t key = a.kidx[b];
-  if (key >= a.nkeys) {
-    if (y == 0) a.status[b] = -3;      // MP_ERR_BAD_ARGUMENT: no such key in the set
-    key = 0;
-  }
+  bool named;
+  const uint32_t key = keyset_slot(a.kidx, b, a.nkeys, a.live, named);
+  if (!named && y == 0) a.status[b] = -3;      // MP_ERR_BAD_ARGUMENT: no such key in the set, or an empty slot
   a.out[(size_t)b * W + y] = a.wire[(size_t)key * W + y];
 }
 MP_KERNEL(k_gather_keys, GatherKeysArgs, body_gather_keys)

@@ -231,6 +231,16 @@ class DLCards:
             self._tables[key] = t
         return t
 
+    def key_set(self, pp, capacity):
+        """a key set of `capacity` empty slots on a table of its own of `pp` (include/mpshuffle.h, "key sets whose slots change"): fill
+        and change it with KeySet.update / update_dev / clear, name its slots as (key_set, index) in verify_shuffle_chains and through
+        key_set.table's _keyset_dev calls.  close() the set, then key_set.table, when done"""
+        try:
+            t = _native.Table(self.engine, pp.m, pp.n, pp.raw, None, self.fb_bits)
+            return t.keyset_empty(capacity)
+        except _native.NativeError as e:
+            raise CardProtocolError.io(str(e))
+
     def params_table(self, pp):
         """the coalescing table of `pp` (DLCards(coalesce=...)): parameters only, one per (m, n, params), created on first use"""
         key = (pp.m, pp.n, pp.raw)
@@ -465,6 +475,11 @@ class DLCards:
     #    statements are assembled on the device)                                                    [REF examples/round.rs:228-262]
     def _deal_shape(self, shared_keys, key_index, inputs, input_bytes):
         pb = self.engine.point_bytes
+        if isinstance(shared_keys, _native.KeySet):      # dealing by index: key_index names slots of the set
+            if not inputs or len(key_index) != len(inputs) or any(len(bytes(c)) != input_bytes for c in inputs) or \
+                    any(not 0 <= int(k) < 1 << 32 for k in key_index):
+                raise CardProtocolError.io("at least one card of %d bytes, and one slot of the key set per card" % input_bytes)
+            return
         if not shared_keys or not inputs or len(key_index) != len(inputs):
             raise CardProtocolError.io("at least one key and one card, and one key index per card")
         if any(len(bytes(k)) != pb for k in shared_keys) or any(len(bytes(c)) != input_bytes for c in inputs):
@@ -478,9 +493,12 @@ class DLCards:
         if len(rng_seeds) != len(inputs) or len(factors) != len(inputs) or any(len(bytes(s)) != 32 for s in rng_seeds):
             raise CardProtocolError.io("one 32-byte prover seed and one masking factor per card")
         try:
-            out, prf, st = self._t(pp).mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index],
-                                                  b"".join(bytes(c) for c in inputs),
-                                                  _scalar_bytes([f % CURVE_ORDERS[self.curve] for f in factors]), b"".join(bytes(s) for s in rng_seeds))
+            rest = (b"".join(bytes(c) for c in inputs), _scalar_bytes([f % CURVE_ORDERS[self.curve] for f in factors]),
+                    b"".join(bytes(s) for s in rng_seeds))
+            if isinstance(shared_keys, _native.KeySet):
+                out, prf, st = shared_keys.table.mask_batch_keyset(shared_keys, kind, [int(k) for k in key_index], *rest)
+            else:
+                out, prf, st = self._t(pp).mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index], *rest)
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         cb, psz = 2 * pb, 2 * pb + 32
@@ -494,16 +512,20 @@ class DLCards:
                 any(len(bytes(p)) != 2 * pb + 32 for p in proofs):
             raise CardProtocolError.io("one %d-byte masked card and one %d-byte proof per card" % (2 * pb, 2 * pb + 32))
         try:
-            st = self._t(pp).verify_mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index],
-                                               b"".join(bytes(c) for c in inputs), b"".join(bytes(c) for c in masked_cards),
-                                               b"".join(bytes(p) for p in proofs))
+            rest = (b"".join(bytes(c) for c in inputs), b"".join(bytes(c) for c in masked_cards), b"".join(bytes(p) for p in proofs))
+            if isinstance(shared_keys, _native.KeySet):
+                st = shared_keys.table.verify_mask_batch_keyset(shared_keys, kind, [int(k) for k in key_index], *rest)
+            else:
+                st = self._t(pp).verify_mask_batch(kind, b"".join(bytes(k) for k in shared_keys), [int(k) for k in key_index], *rest)
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         return [None if v == 0 else CryptoError(self.engine.check_name(v)) if v > 0 else CardProtocolError.io(self.engine.check_name(v)) for v in st]
 
     def deal(self, rng_seeds, pp, shared_keys, key_index, cards, factors):
         """`mask` for many cards: card i (a plaintext card) is masked under shared_keys[key_index[i]] with the factor factors[i];
-        rng_seeds: one fresh 32-byte seed per card -> per card (MaskedCard, ZKProofMasking), or the CardProtocolError of its lane"""
+        rng_seeds: one fresh 32-byte seed per card -> per card (MaskedCard, ZKProofMasking), or the CardProtocolError of its lane.
+        Here and in verify_deal, deal_remask and verify_deal_remask, shared_keys may be a key set (key_set()): key_index[i] then names a
+        slot, and the products with the key come from the set's tables (mp_mask_batch_keyset / mp_verify_mask_batch_keyset)"""
         return self._deal(_native.Table.DEAL_MASK, rng_seeds, pp, shared_keys, key_index, cards, factors)
 
     def verify_deal(self, pp, shared_keys, key_index, cards, masked_cards, proofs):
@@ -519,11 +541,13 @@ class DLCards:
         """`verify_remask` for many cards -> per card None, or the error `verify_remask` raises for it"""
         return self._verify_deal(_native.Table.DEAL_REMASK, pp, shared_keys, key_index, original_cards, remasked_cards, proofs)
 
-    def compute_aggregate_keys(self, pp, tables):
+    def compute_aggregate_keys(self, pp, tables, into=None):
         """`compute_aggregate_key` for many tables: tables = [[(pk, proof, player_public_info)]], at least one player at each (tables
         of one size go through mp_aggregate_keys_batch, tables of different sizes through mp_aggregate_keys_ragged_batch)
         -> per table the AggregatePublicKey, or the error `compute_aggregate_key` raises for it:
-        CardProtocolError("ProofVerificationError", CryptoError("Schnorr Identification")) / CardProtocolError.io(...)"""
+        CardProtocolError("ProofVerificationError", CryptoError("Schnorr Identification")) / CardProtocolError.io(...).
+        into=(key_set, slots): the sums also go straight into slots[k] of the key set, on the device (mp_keyset_seat_ragged_batch); a
+        table that gets an error here, or whose keys sum to the identity (the error of a bad encoding), leaves its slot EMPTY"""
         pb = self.engine.point_bytes
         if not tables or any(not t for t in tables):
             raise CardProtocolError.io("at least one table, and at least one player at each")
@@ -533,7 +557,11 @@ class DLCards:
         try:
             lanes = (b"".join(bytes(pk) for pk, _, _ in rows), b"".join(bytes(proof) for _, proof, _ in rows),
                      b"".join(self.engine.blake2s(KEY_OWN_RNG_SEED + bytes(info)) for _, _, info in rows))
-            if all(len(t) == len(tables[0]) for t in tables):
+            if into is not None:
+                kset, slots = into
+                keys, _, ts, ss = kset.seat([len(t) for t in tables], [int(v) for v in slots], *lanes)
+                ts = [v if v != 0 else w for v, w in zip(ts, ss)]
+            elif all(len(t) == len(tables[0]) for t in tables):
                 keys, _, ts = self._t(pp).aggregate_keys_batch(len(tables), len(tables[0]), *lanes)
             else:
                 keys, _, ts = self._t(pp).aggregate_keys_ragged_batch([len(t) for t in tables], *lanes)
@@ -603,13 +631,22 @@ class DLCards:
     def verify_shuffle_chains(self, pp, chains):
         """the shuffle chains of many tables, of different lengths, in one call (mp_verify_shuffle_chain_ragged).  chains: per table
         (key_or_keys, decks, proofs) -- the table's aggregate key, or one key per link; links + 1 decks, deck j + 1 the output of link j;
-        one proof per link, at least one -> per table a list with, per link, None or the error verify_shuffle raises for it"""
+        one proof per link, at least one -> per table a list with, per link, None or the error verify_shuffle raises for it.
+        With (key_set, index) in place of the key of EVERY table, all of one key_set(): the keys are named by index
+        (mp_verify_shuffle_chain_ragged_keyset), and a table on an empty slot gets the error of a bad argument on every link"""
         pb, N = self.engine.point_bytes, pp.m * pp.n
         psz = self.engine.proof_size(pp.m, pp.n)
         if not chains:
             raise CardProtocolError.io("at least one table")
         links, keys, decks, proofs = [], [], [], []
+        by_index = [isinstance(c[0], tuple) and len(c[0]) == 2 and isinstance(c[0][0], _native.KeySet) for c in chains]
+        if any(by_index) and (not all(by_index) or any(c[0][0] is not chains[0][0][0] for c in chains)):
+            raise CardProtocolError.io("keys by index: (key_set, index) for every table, all of one key set")
+        kset, indices = (chains[0][0][0], [int(c[0][1]) for c in chains]) if by_index[0] else (None, None)
+        spare = bytes(pb)
         for key, dks, prfs in chains:
+            if kset is not None:
+                key = spare
             ks = [bytes(key)] * len(prfs) if isinstance(key, (bytes, bytearray)) else [bytes(k) for k in key]
             if not prfs or len(dks) != len(prfs) + 1 or len(ks) != len(prfs):
                 raise CardProtocolError.io("a chain is at least one link: links + 1 decks, one proof per link, one key or one key per link")
@@ -621,7 +658,10 @@ class DLCards:
             decks += [b"".join(bytes(c) for c in d) for d in dks]
             proofs += [bytes(p) for p in prfs]
         try:
-            st = self.table(pp, keys[0]).verify_shuffle_chain_ragged(links, b"".join(decks), b"".join(proofs), b"".join(keys))
+            if kset is not None:
+                st = kset.table.verify_shuffle_chain_ragged_keyset(kset, links, indices, b"".join(decks), b"".join(proofs))
+            else:
+                st = self.table(pp, keys[0]).verify_shuffle_chain_ragged(links, b"".join(decks), b"".join(proofs), b"".join(keys))
         except _native.NativeError as e:
             raise CardProtocolError.io(str(e))
         words = [None if s == 0 else (CryptoError(self.engine.check_name(s)) if s > 0 else CardProtocolError.io(self.engine.check_name(s)))
